@@ -5,8 +5,11 @@ channels 2 16 32 64 32 16 32 2, batch 4 per GPU, 2x128^3 synthetic volumes, bf16
 A step = ``Learner.train_batch`` (learner/Learner.py:116-130 of the reference): forward + (Dice+Dice)/2 + zero_grad +
 backward + [RCCL all-reduce, bucketed, overlapped with backward] + Adam, without the CPU-side medpy metrics
 (excluded on both sides).  The product's own ``Learner(graph=True)`` replays the step as one hipGraph.
-Prints ONE JSON line on rank 0 (contract in the task statement) with ``roofline`` (dominant kernel family,
-HIP-event timed) and ``cpu_baseline`` (the CPU oracle on the host cores; all cores and 8 threads).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times ``--steps`` steps
+and prints the line; ``--full`` adds what takes runs of its own: ``roofline`` / ``kernels`` (dominant kernel family,
+HIP-event timed eager steps), ``parity`` (the other precision modes against the f32 mode), ``cpu_baseline`` (the CPU
+oracle on the host cores; all cores and 8 threads), ``secondary`` (the other workloads) and the
+input-copy time.  ``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy``.
 
 ``--gpus N`` with no WORLD_SIZE in the environment launches its own N ranks (``python -m torch.distributed.run``)
 BEFORE anything touches the GPU, forwards rank 0's JSON line and exits with the children's status.
@@ -251,6 +254,60 @@ def timed_steps(step, args, world, dev):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
     return dt, out
+
+
+DUMP_BYTES = 60 * 1000 * 1000     # --dump-outputs writes at most this much (a larger set: a seeded sample of every array)
+
+
+def keep_last_dto(learner):
+    """--dump-outputs: remember the DTO of the learner's latest forward (in graph mode the captured one, whose tensors every
+    replay rewrites).  Installed only when dumping, so a plain run's step is untouched."""
+    seen = {}
+    inner = learner.inference_step
+
+    def inference_step(batch):
+        seen["dto"] = inner(batch)
+        return seen["dto"]
+    learner.inference_step = inference_step
+    return seen
+
+
+def dto_tensors(dto, prefix):
+    """{"<prefix>_<field>[_<field>...]": tensor} of every tensor leaf under a DTO"""
+    from stroke_prediction_amd.common.dto.Dto import Dto
+    out = {}
+    for key, value in dto:
+        name = "%s_%s" % (prefix, key)
+        if isinstance(value, Dto):
+            out.update(dto_tensors(value, name))
+        elif torch.is_tensor(value):
+            out[name] = value
+    return out
+
+
+def model_state(model):
+    """every floating-point entry of the state dict (parameters and BatchNorm buffers), flattened in key order"""
+    return torch.cat([v.detach().reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()])
+
+
+def dump_outputs(path, arrays):
+    """``path/<name>.npy`` for every array: float64 stays float64, everything else becomes float32.  When the whole set is
+    larger than DUMP_BYTES, every array is cut to the same fraction of its elements (at least one): flat indices drawn by a
+    generator seeded from the array's name, so that two runs with the same arguments sample the same elements."""
+    import numpy as np
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach() for k, v in arrays.items()}
+    total = sum(8 * v.numel() if v.dtype == torch.float64 else 4 * v.numel() for v in arrays.values())
+    for name, v in arrays.items():
+        v = v.cpu().to(torch.float64 if v.dtype == torch.float64 else torch.float32)
+        if total > DUMP_BYTES:
+            keep = max(1, v.numel() * DUMP_BYTES // total)
+            if keep < v.numel():
+                g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+                v = v.reshape(-1)[torch.randint(v.numel(), (keep,), generator=g).sort().values]
+        np.save(os.path.join(path, name + ".npy"), v.numpy())
+    print("bench.py: %d arrays written to %s" % (len(arrays), path), file=sys.stderr)
 
 
 def kernel_profile(eager_step, nsteps, world):
@@ -541,14 +598,17 @@ def bench_unet(args, world, rank, dev, four_scale=False):
     def step():
         return learner.train_batch(batch, 0)
 
+    seen = keep_last_dto(learner) if args.dump_outputs else None
     for _ in range(learner.GRAPH_WARMUP + 1 if use_graph else 0):      # eager warm-ups + capture happen before the timed region
         step()
     dt, last = timed_steps(step, args, world, dev)
     ms = 1e3 * dt / args.steps
+    if args.dump_outputs and rank == 0:      # the last timed step's loss, segmentation and the model it left behind
+        dump_outputs(args.dump_outputs, dict(dto_tensors(seen["dto"].outputs, "outputs"), loss=last.loss, state=model_state(model)))
     # what a loader pays that does NOT write into the step's own buffers: the device-to-device copy of one batch (outside the timed
     # region; reported next to the line so that the resident-input number can be read either way)
     copy_us = None
-    if use_graph and not os.environ.get("SP_BENCH_COPY_INPUTS") and batch["images"].data_ptr() != images.data_ptr():
+    if args.full and use_graph and not os.environ.get("SP_BENCH_COPY_INPUTS") and batch["images"].data_ptr() != images.data_ptr():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(20):
@@ -678,7 +738,7 @@ def bench_unet_infer(args, world, rank, dev):
     def step():
         with torch.no_grad():
             dto = model(UnetDtoUtil.init_dto(images, labels[:, 0:1], labels[:, 1:2]))
-        return dto.outputs.core
+        return dto.outputs
 
     for _ in range(3):
         step()
@@ -687,8 +747,10 @@ def bench_unet_infer(args, world, rank, dev):
     if not args.no_graph and world == 1:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            step()
-    dt, _ = timed_steps((lambda: graph.replay()) if graph is not None else step, args, world, dev)
+            captured = step()
+    dt, last = timed_steps((lambda: graph.replay()) if graph is not None else step, args, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dto_tensors(captured if graph is not None else last, "outputs"))
     vox = world * args.batch * size[0] * size[1] * size[2] * args.steps
     res = {"metric": "inference voxels/sec, 3D U-Net Bx2x%d^3 (eval forward)" % args.size, "value": vox / dt, "unit": "voxels/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
@@ -729,10 +791,15 @@ def bench_cae(args, world, rank, dev):
     def step():
         return learner.train_batch(batch, epoch)
 
+    seen = keep_last_dto(learner) if args.dump_outputs else None
     for _ in range(learner.GRAPH_WARMUP + 1 if use_graph else 0):
         step()
     dt, last = timed_steps(step, args, world, dev)
     ms = 1e3 * dt / args.steps
+    if args.dump_outputs and rank == 0:
+        dto = seen["dto"]
+        dump_outputs(args.dump_outputs, dict(dto_tensors(dto.latents, "latents"), **dto_tensors(dto.reconstructions, "reconstructions"),
+                                             loss=last.loss, state=model_state(cae)))
     vox = world * args.batch * d * hw * hw * args.steps
     res = {"metric": "train-step voxels/sec, CAE Bx1xDx128x128 (3 encoder + 4 decoder passes)", "value": vox / dt,
            "unit": "voxels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
@@ -766,7 +833,7 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 4; unet4: 2 -- BatchNorm training needs more than one sample, as Learner asserts)")
     ap.add_argument("--size", type=int, default=None, help="cubic input size (default 128; unet4: 256)")
     ap.add_argument("--dtype", default="bf16", choices=DTYPES)
-    ap.add_argument("--no-secondary", action="store_true", help="default run only: skip the compact results of the other workloads")
+    ap.add_argument("--no-secondary", action="store_true", help="--full run of the default workload only: skip the compact results of the other workloads")
     ap.add_argument("--workload", default="unet", choices=["unet", "cae", "unet-infer", "unet4"],
                     help="unet = BASELINE configs[1] (headline); cae = configs[2]: CAE 1 16 24 32 100 800 1, 3 enc + 4 dec passes; "
                          "unet4 = configs[4] topology (4-scale U-Net 2 32 64 128 256 128 64 32 [32] 2, default 256^3); "
@@ -782,7 +849,18 @@ def main():
     ap.add_argument("--no-buckets", action="store_true", help="multi-GPU: one blocking all-reduce after backward instead of overlapped buckets")
     ap.add_argument("--layers", action="store_true", help="print per-layer conv kernel timings to stderr")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from Python instead of replaying a hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: kernel timing and rooflines, the "
+                         "precision parity leg, the CPU baseline, the secondary workloads and the input-copy time (each still "
+                         "subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (outputs, loss, model state) as DIR/<name>.npy, float32 / float64, "
+                         "at most 60 MB in all (a larger set: the same seeded sample fraction of every array)")
     args = ap.parse_args()
+    if args.layers and not args.full:
+        ap.error("--layers prints the kernel timing of --full")
+    if not args.full:      # a plain run: set up, warm up, time the steps, print the line
+        args.no_kernel_timing = args.no_parity = args.no_cpu_baseline = args.no_secondary = True
     if args.batch is None:
         args.batch = 2 if args.workload == "unet4" else 4
     if args.size is None:
@@ -852,7 +930,7 @@ def run_workload(args, world, rank, dev):
 
 
 def secondary_workloads(args, dev):
-    """The other workloads of BASELINE.json / SURVEY 8 under the same clock as the headline line (the driver runs only the
+    """The other workloads of BASELINE.json / SURVEY 8 under the same clock as the headline line (``--full`` runs of the
     default command): each with its own model, warm-up and timed region, AFTER the headline's timed region has closed;
     compact results (the full line of each is what `bench.py --workload ... ` prints).  Bounded: 10 timed steps each, one
     timed CPU-oracle step where a CPU leg is given."""
@@ -874,7 +952,7 @@ def secondary_workloads(args, dev):
         if over["dtype"] not in DTYPES:
             continue
         a = copy.copy(args)
-        a.steps, a.warmup, a.layers, a.no_parity, a.torch_gpu_baseline = 10, 3, False, True, False
+        a.steps, a.warmup, a.layers, a.no_parity, a.torch_gpu_baseline, a.dump_outputs = 10, 3, False, True, False, None
         a.no_cpu_baseline = not cpu or args.no_cpu_baseline
         a.cpu_steps = 1
         for k, v in over.items():

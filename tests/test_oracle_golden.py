@@ -206,6 +206,13 @@ def test_cae_phase2_learners_match_reference(golden_dir):
         np.testing.assert_allclose(rec_in[k].detach()[:, 0, d // 2, 60:68, 60:68].numpy(), fx["rec_in_crop/" + k], rtol=1e-4, atol=1e-5)
     loss = nets.cae_prediction_loss(lat_in, rec_in, lat_gt, lesion)
     assert abs(loss.item() - float(fx["loss"])) < 2e-6
+    # gradient norms from a float64 pass of the same restatement: encoder.0.weight is one element whose gradient (~1e-5)
+    # cancels over the whole batch, and float32 sums move it by up to 2.4e-3 relative with the host's thread count
+    f64 = lambda sd: {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}  # noqa: E731
+    sd_enc = _leafify(f64(W.make_state_dict(W.enc_spec(ch), seed + 1)))
+    lat_in, rec_in, lat_gt, _ = nets.cae_prediction_forward(f64(sd_cae), sd_enc, images[:, 0:1].double(), images[:, 1:2].double(),
+                                                            core.double(), penu.double(), lesion.double(), step.double())
+    loss = nets.cae_prediction_loss(lat_in, rec_in, lat_gt, lesion.double())
     names = nets.trainable(sd_enc)
     grads = torch.autograd.grad(loss, [sd_enc[k] for k in names])
     for k, g in zip(names, grads):
