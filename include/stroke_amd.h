@@ -578,6 +578,17 @@ int sp_ncdhw_to_cl(const float* src, void* dst, int32_t dtype, int32_t B, int32_
                    sp_stream_t stream);
 int sp_cl_to_ncdhw(const void* src, float* dst, int32_t dtype, int32_t B, int32_t C, int64_t DHW, int32_t CP,
                    sp_stream_t stream);
+/* stack input of the CTP-conditioned CAE encoder (Enc3DCtp; reference Cae3D.py:151-165), all G <= 4 passes of one encoder
+ * call in one launch: x0[g B + b][d][h][w][0..CP) = (label_g, CBV, TTD, 0, ...), channels-last in dtype, bit-equal to
+ * crop -> cat -> sp_ncdhw_to_cl.  labels / label_bstride: HOST arrays of G fp32 device pointers (B, 1, D, H, W) and their
+ * batch strides in elements (spatial dimensions contiguous).  cbv / ttd: fp32 (B, 1, Dp, Hp, Wp) with batch strides; the
+ * crop starts at (oD, oH, oW).  sums (training; null in eval): per-pass BatchNorm statistics of the stored values added into
+ * G regions of sums_gstride doubles, each [nrep][CP][2] replica rows (the grouped StackContext layout); CBV / TTD are
+ * reduced once and added to every region. */
+int sp_ctp_stack_input(const float* const* labels, const int64_t* label_bstride, int32_t G, int32_t B, int32_t D, int32_t H,
+                       int32_t W, const float* cbv, int64_t cbv_bstride, const float* ttd, int64_t ttd_bstride, int32_t Dp,
+                       int32_t Hp, int32_t Wp, int32_t oD, int32_t oH, int32_t oW, void* x0, int32_t dtype, int32_t CP,
+                       double* sums, int64_t sums_gstride, int32_t nrep, sp_stream_t stream);
 
 /* ------------------------------------------------------------------ BatchNorm3d pieces (Unet3D.py:18,21; Cae3D.py:40..217)
  * sums[c] = (sum x, sum x^2) over all nvox voxels of a channels-last tensor */

@@ -56,6 +56,17 @@ class CaeInference(Inference):
         dto.given_variables.gtruth.lesion = labels[:, 2:3].float()
         return dto
 
+    def init_ctp_variables(self, batch: dict, dto: CaeDto):
+        """the CT-perfusion maps next to the labels: ``images[:, 0:1]`` (CBV) and ``[:, 1:2]`` (TTD), the modalities of
+        train_shape_reconstruction_with_ctp.py in its order, padded as the data pipeline left them.  The reference's
+        inference passes None here (CaeInference.py:46-47), so its CTP-conditioned CAE could not run."""
+        images = batch[data.KEY_IMAGES]
+        if self.is_cuda:
+            images = images.to(self._device(), non_blocking=True)
+        dto.given_variables.inputs.core = images[:, 0:1].float()
+        dto.given_variables.inputs.penu = images[:, 1:2].float()
+        return dto
+
     def infer(self, dto: CaeDto):
         return self._model(dto)
 
@@ -63,4 +74,6 @@ class CaeInference(Inference):
         dto = self.init_clinical_variables(batch, step)
         dto.mode = CaeDtoUtil.FLAG_GTRUTH
         dto = self.init_gtruth_segm_variables(batch, dto)
+        if getattr(self._model, "USES_CTP_INPUTS", False):       # Cae3DCtp: every other model leaves the inputs alone
+            dto = self.init_ctp_variables(batch, dto)
         return self.infer(dto)

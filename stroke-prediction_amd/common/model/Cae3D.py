@@ -7,7 +7,10 @@ The ``torch.nn`` members are parameter containers; every encoder / decoder call 
 the operand load, ELU / Sigmoid and the next layer's batch statistics fused into the conv epilogues,
 strided and transposed convolutions through the same table-driven implicit-GEMM kernel).  The latent
 interpolation (Cae3D.py:78-89) stays a three-operand torch expression on B x 800 x 1 x 10 x 10 values.
-``Enc3DStep`` / ``Enc3DCtp`` (learned step, CTP-conditioned encoder) are outside the accelerated path.
+``Enc3DStep`` (learned step) adds three torch 1x1x1 convolutions on B x 5 values to the fused encoder.  ``Enc3DCtp`` /
+``Cae3DCtp`` (the CTP-conditioned CAE, Cae3D.py:145-169,258-260) run ``Enc3D``'s stack with a three-channel input whose
+construction -- crop of the CBV / TTD maps, concatenation with each shape label, layout and batch statistics -- is one
+kernel per encoder call (csrc/sp_ctp.hip).
 """
 import contextlib
 import os
@@ -98,7 +101,7 @@ class _StackFn(torch.autograd.Function):
         ctx.concurrent = bool(opts.get("concurrent"))
         with (_O.no_fork() if ctx.concurrent else contextlib.nullcontext()):
             out = sc.forward(x, module._param_dict(), module._buffer_dict(), module.training, bump_nbt=opts.get("bump_nbt", True),
-                             order=opts.get("order"))
+                             order=opts.get("order"), ctp=opts.get("ctp"))
         ctx.home = opts.get("home")              # the stream the call came from (concurrent passes: joined again after backward)
         ctx.module, ctx.sc = module, sc
         ctx.frozen = module._stack_frozen()      # only the input needs a gradient: data-gradient-only backward
@@ -175,14 +178,16 @@ CAE_BATCHED = int(os.environ.get("SP_CAE_BATCHED", "1"))
 
 
 class _StackManyFn(torch.autograd.Function):
-    """All passes of one encoder / decoder call as one autograd node: forward(module, n, x_0 .. x_{n-1}, *params) -> n outputs."""
+    """All passes of one encoder / decoder call as one autograd node: forward(module, n, ctp, x_0 .. x_{n-1}, *params) -> n outputs.
+    ctp (a cae_engine.CtpInput, or None): the stack input of a CTP-conditioned encoder call, built from the labels x_k and the
+    CBV / TTD maps by one kernel; those are data, so the node then has no input gradient."""
 
     @staticmethod
-    def forward(ctx, module, n, *args):
+    def forward(ctx, module, n, ctp, *args):
         xs, B = args[:n], args[0].shape[0]
         key, sc = module._pool().acquire(n * B, tuple(xs[0].shape[2:]), module._dtype_code(), xs[0].device, groups=n)
-        x = torch.cat([t.float() for t in xs], 0)
-        out = sc.forward(x, module._param_dict(), module._buffer_dict(), module.training)
+        x = torch.cat([t.float() for t in xs], 0) if ctp is None else None
+        out = sc.forward(x, module._param_dict(), module._buffer_dict(), module.training, ctp=ctp)
         ctx.module, ctx.sc, ctx.n, ctx.B = module, sc, n, B
         ctx.nparams = len(args) - n
         ctx.frozen = module._stack_frozen()
@@ -191,7 +196,7 @@ class _StackManyFn(torch.autograd.Function):
             module._begin_step()
             module._n_out = getattr(module, "_n_out", 0) + 1
         ctx.training = module.training
-        ctx.need_dx = any(t.requires_grad for t in xs)
+        ctx.need_dx = ctp is None and any(t.requires_grad for t in xs)
         ctx.save_for_backward(out)
         outs = tuple(out[i * B:(i + 1) * B] for i in range(n))
         return outs
@@ -214,7 +219,7 @@ class _StackManyFn(torch.autograd.Function):
         if ctx.frozen:
             dx = _frozen_backward(ctx, module, sc, dout, out)
             dxs = tuple(None for _ in range(n)) if dx is None else tuple(dx[i * B:(i + 1) * B] for i in range(n))
-            return (None, None) + dxs + tuple(None for _ in range(ctx.nparams))
+            return (None, None, None) + dxs + tuple(None for _ in range(ctx.nparams))
         names, views, inplace = module._grad_targets()
         dx = sc.backward(dout, out, module._param_dict(), dict(zip(names, views)), ctx.need_dx)
         ctx.lease.release()
@@ -222,7 +227,7 @@ class _StackManyFn(torch.autograd.Function):
         if module._n_out == 0:
             module._stack_grads_final()
         dxs = tuple(None for _ in range(n)) if dx is None else tuple(dx[i * B:(i + 1) * B] for i in range(n))
-        return (None, None) + dxs + tuple(None if inplace else v for v in views)
+        return (None, None, None) + dxs + tuple(None if inplace else v for v in views)
 
 
 class CaeBase(FlatParamsMixin, nn.Module):
@@ -275,19 +280,22 @@ class CaeBase(FlatParamsMixin, nn.Module):
         opts = opts or {}
         key, sc = opts.get("sc") or self._pool().acquire(x.shape[0], tuple(x.shape[2:]), self._dtype_code(), x.device, lane=opts.get("lane", 0))
         out = sc.forward(x, self._param_dict(), self._buffer_dict(), self.training, bump_nbt=opts.get("bump_nbt", True),
-                         order=opts.get("order"))
+                         order=opts.get("order"), ctp=opts.get("ctp"))
         self._pool().release(key, sc)
         return out
 
-    def _run_stack_many(self, xs):
+    def _run_stack_many(self, xs, ctp=None):
         """The passes of one encoder / decoder call (``None`` entries stay ``None``): one after the other on the current
-        stream, or -- see CAE_STREAMS -- each on its own stream with the outputs joined back before returning."""
+        stream, or -- see CAE_STREAMS -- each on its own stream with the outputs joined back before returning.
+        ctp (Enc3DCtp: a cae_engine.CtpInput of the call's CBV / TTD maps): the xs are the shape labels, and every pass's stack
+        input is built from its label and the maps (csrc/sp_ctp.hip)."""
         idx = [i for i, x in enumerate(xs) if x is not None]
         if CAE_BATCHED and len(idx) > 1 and xs[idx[0]].is_cuda and next(self.parameters()).is_cuda and \
                 all(xs[i].shape == xs[idx[0]].shape and xs[i].device == xs[idx[0]].device for i in idx):
-            return self._run_stack_batched(xs, idx)
+            return self._run_stack_batched(xs, idx, ctp)
+        one = (lambda x: None) if ctp is None else (lambda x: None if x is None else dict(ctp=ctp.with_labels([x])))
         if len(idx) <= 1 or not xs[idx[0]].is_cuda or CAE_STREAMS == 0:
-            return [self._run_stack(x) for x in xs]
+            return [self._run_stack(x, one(x)) for x in xs]
         # Pass k always runs in the contexts of lane k (their own packed weights and workspaces), whether or not the lanes run
         # concurrently right now: the eager warm-up steps of Learner(graph=True) thereby create, on one stream, exactly the
         # contexts the captured step uses (building one uploads tables, which a capturing stream may not do).
@@ -319,7 +327,7 @@ class CaeBase(FlatParamsMixin, nn.Module):
             rec = [torch.cuda.Event() for _ in range(nlayers)] if (conc and training and lane + 1 < n and "noorder" not in _DBG) else None
             with torch.cuda.stream(s):
                 outs[i] = self._run_stack(xs[i], dict(lane=lane, sc=scs[lane], concurrent=conc, home=main, bump_nbt=nbt is None,
-                                                      order=(prev, rec) if (conc and training) else None))
+                                                      order=(prev, rec) if (conc and training) else None, **(one(xs[i]) or {})))
             prev = rec
         if conc:
             for lane, i in enumerate(idx):
@@ -329,19 +337,21 @@ class CaeBase(FlatParamsMixin, nn.Module):
                         outs[i].record_stream(main)
         return outs
 
-    def _run_stack_batched(self, xs, idx):
+    def _run_stack_batched(self, xs, idx, ctp=None):
         """all passes of the call in ONE grouped context (CAE_BATCHED)"""
         self._ensure_flat()
         n = len(idx)
         ins = [xs[i] for i in idx]
         params = [p for _, p in self.named_parameters()]
         outs = list(xs)
+        ctp = None if ctp is None else ctp.with_labels(ins)
         if torch.is_grad_enabled() and (any(t.requires_grad for t in ins) or not self._stack_frozen()):
-            res = _StackManyFn.apply(self, n, *ins, *params)
+            res = _StackManyFn.apply(self, n, ctp, *ins, *params)
         else:
             B = ins[0].shape[0]
             key, sc = self._pool().acquire(n * B, tuple(ins[0].shape[2:]), self._dtype_code(), ins[0].device, groups=n)
-            out = sc.forward(torch.cat([t.float() for t in ins], 0), self._param_dict(), self._buffer_dict(), self.training)
+            x = torch.cat([t.float() for t in ins], 0) if ctp is None else None
+            out = sc.forward(x, self._param_dict(), self._buffer_dict(), self.training, ctp=ctp)
             self._pool().release(key, sc)
             res = tuple(out[i * B:(i + 1) * B] for i in range(n))
         for i, r in zip(idx, res):
@@ -483,12 +493,81 @@ class Enc3DStep(Enc3D):
         return step
 
 
-class Enc3DCtp(Enc3D):
-    """CTP-conditioned encoder (reference Cae3D.py:145-169): only reachable from ``train_shape_reconstruction_with_ctp.py``,
-    which passes keyword arguments the reference classes do not accept -- outside the accelerated path."""
+class CtpChannelsError(ValueError, NotImplementedError):
+    """``Enc3DCtp`` with ``channels[0] != 3``: a bad argument, and a configuration this encoder does not implement (the
+    reference asserts only ``channels[0] > 2``, but its first convolution takes exactly the three concatenated channels)"""
 
-    def __init__(self, *a, **k):
-        raise NotImplementedError("Enc3DCtp is outside the MI355X path (SURVEY.md 2.1 row 2: not used by the two named scripts)")
+
+class Enc3DCtp(Enc3D):
+    """CTP-conditioned encoder (reference Cae3D.py:145-169): every pass encodes cat(shape label, CBV, TTD), where CBV / TTD are
+    ``given_variables.inputs.core`` / ``.penu`` (the padded perfusion maps) cropped by ``padding`` (D, H, W voxels per side) to
+    the label's extent.  The three-channel stack input of all passes of a call, and its first BatchNorm's batch statistics,
+    are built by ONE kernel (csrc/sp_ctp.hip; labels and maps are data: no input gradient); the convolution stack is
+    ``Enc3D``'s with channels[0] = 3, and the state_dict keys are the reference's (``encoder.0`` = BatchNorm3d(3), ...).
+
+    Where the reference is undefined:
+      * ``channels[0]`` must be exactly 3 -- the reference asserts > 2, but its first convolution takes exactly the three
+        concatenated channels -- ``CtpChannelsError`` (a ``ValueError``) otherwise;
+      * ``padding`` is required, as in the reference (its default None is refused with ``ValueError``; it exists so that the
+        channel count is checked first);
+      * a padding of 0 on an axis means "no crop on that axis" (the reference's ``x[0:-0]`` slice would be empty);
+      * CTP extents that, cropped, differ from the label extents raise ``ValueError``;
+      * only the ground-truth branch runs (FLAG_GTRUTH / FLAG_DEFAULT); ``latents.inputs`` stays empty, as in the reference."""
+    USES_CTP_INPUTS = True      # CaeInference.inference_step fills given_variables.inputs with the batch's CBV / TTD images
+
+    def __init__(self, size_input_xy, size_input_z, channels, n_ch_global, alpha, padding=None, dtype="bf16"):
+        if len(channels) < 1 or int(channels[0]) != 3:
+            raise CtpChannelsError("Enc3DCtp needs channels[0] == 3, got %r: every encoder pass sees cat(label, CBV, TTD), the three "
+                             "input channels of its first convolution" % (list(channels)[:1],))
+        if padding is None:
+            raise ValueError("Enc3DCtp: padding (D, H, W voxels per side of the CBV / TTD volumes) is required")
+        try:
+            pad = tuple(int(p) for p in padding)
+        except TypeError:
+            raise ValueError("Enc3DCtp: padding must be three voxel counts (D, H, W), got %r" % (padding,))
+        if len(pad) != 3 or min(pad) < 0:
+            raise ValueError("Enc3DCtp: padding must be three non-negative voxel counts (D, H, W), got %r" % (padding,))
+        super().__init__(size_input_xy, size_input_z, channels, n_ch_global, alpha, dtype=dtype)
+        self._padding = pad
+
+    def _crop_offsets(self, label_shape, ctp_shape):
+        """the corner of the label's extent inside the padded CTP volume, per axis: ``padding`` (0: no crop)"""
+        offs = []
+        for ax, (n, m, p) in enumerate(zip(label_shape[2:], ctp_shape[2:], self._padding)):
+            if (m - 2 * p if p > 0 else m) != n:
+                raise ValueError("Enc3DCtp: the CTP maps %s cropped by padding %s are not the label extent %s (axis %d)"
+                                 % (tuple(ctp_shape[2:]), self._padding, tuple(label_shape[2:]), ax))
+            offs.append(p)
+        return tuple(offs)
+
+    def _ctp_input(self, inputs, labels):
+        from stroke_prediction_amd.runtime.cae_engine import CtpInput
+        cbv, ttd = inputs.core, inputs.penu
+        if cbv is None or ttd is None:
+            raise ValueError("Enc3DCtp needs the CT-perfusion maps: given_variables.inputs.core (CBV) and .penu (TTD)")
+        ref = next(t for t in labels if t is not None)
+        for t in (cbv, ttd):
+            if t.dim() != 5 or t.shape[1] != 1 or t.shape[0] != ref.shape[0] or t.shape != cbv.shape:
+                raise ValueError("Enc3DCtp: CBV / TTD must be (B, 1, D, H, W) volumes of the labels' batch, got %s and %s"
+                                 % (tuple(cbv.shape), tuple(ttd.shape)))
+        offs = self._crop_offsets(ref.shape, cbv.shape)
+
+        def data(t):      # fp32, contiguous spatial dimensions (a batch stride is fine: labels[:, k:k+1] views are not copied)
+            t = t.detach().float()
+            return t if t.stride()[2:] == (t.shape[3] * t.shape[4], t.shape[4], 1) else t.contiguous()
+        return [None if t is None else data(t) for t in labels], CtpInput([], data(cbv), data(ttd), offs)
+
+    def forward(self, dto: CaeDto):
+        step = self._get_step(dto)
+        if dto.flag == CaeDtoUtil.FLAG_GTRUTH or dto.flag == CaeDtoUtil.FLAG_DEFAULT:
+            assert dto.latents.gtruth._is_empty()
+            gt, lat = dto.given_variables.gtruth, dto.latents.gtruth
+            labels = [gt.core, gt.penu, gt.lesion]
+            if any(t is not None for t in labels):
+                labels, ctp = self._ctp_input(dto.given_variables.inputs, labels)
+                lat.core, lat.penu, lat.lesion = self._run_stack_many(labels, ctp=ctp)
+            lat.interpolation = self._interpolate(lat.core, lat.penu, step)
+        return dto
 
 
 class Dec3D(CaeBase):
@@ -551,3 +630,13 @@ class Cae3D(FlatParamsMixin, nn.Module):
                   "grad_sync", "grad_bucket_ready", "_bucket_hi", "_grads_synced", "_n_out"):
             state.pop(k, None)
         return state
+
+
+class Cae3DCtp(Cae3D):
+    """The CTP-conditioned CAE (reference Cae3D.py:258-260): an ``Enc3DCtp`` and a ``Dec3D``.  ``USES_CTP_INPUTS``:
+    ``CaeInference.inference_step`` puts the batch's CBV / TTD images (``images[:, 0:1]`` / ``[:, 1:2]``) into
+    ``given_variables.inputs``, which the reference's inference left ``None``."""
+    USES_CTP_INPUTS = True
+
+    def __init__(self, enc: Enc3DCtp, dec: Dec3D):
+        super().__init__(enc, dec)

@@ -85,12 +85,19 @@ class StackContext:
                               and dtype == L.SP_BF16 and last.cpi == 16 and n >= 2)
         self._out_sums = self._out_g = None
 
-    def forward(self, x, params, bufs, training, bump_nbt=True, order=None):
+    def forward(self, x, params, bufs, training, bump_nbt=True, order=None, ctp=None):
         """x: (B, cin, D, H, W) fp32 on the device -> (B, cout, D', H', W') fp32.
         order = (wait, record): per-layer event lists of concurrently running passes of one stack (Cae3D._run_stack_many) --
         layer i starts after the previous pass recorded wait[i], and records record[i] when its own work is enqueued, so the
-        BatchNorm running statistics are updated in pass order, as by the reference's sequential calls (Cae3D.py:105-107)."""
-        assert tuple(x.shape) == (self.batch, self.cin) + self.in_dims, (tuple(x.shape), self.in_dims)
+        BatchNorm running statistics are updated in pass order, as by the reference's sequential calls (Cae3D.py:105-107).
+        ctp (a CtpInput; x is then None): the stack input and its batch statistics come from the labels and CBV / TTD maps of a
+        CTP-conditioned encoder call, built by one kernel (csrc/sp_ctp.hip) instead of sp_ncdhw_to_cl + sp_bn_stats."""
+        if ctp is None:
+            assert tuple(x.shape) == (self.batch, self.cin) + self.in_dims, (tuple(x.shape), self.in_dims)
+        else:
+            lab = ctp.labels[0]
+            assert self.cin == 3 and len(ctp.labels) * lab.shape[0] == self.batch and tuple(lab.shape[2:]) == self.in_dims, \
+                (len(ctp.labels), tuple(lab.shape), self.batch, self.in_dims, self.cin)
         self.scratch.zero()
         wait_ev, rec_ev = order if order is not None else (None, None)
         if training and bump_nbt and "__nbt_flat__" in bufs:
@@ -102,12 +109,16 @@ class StackContext:
                       if not l.fold and not l.fold_groups and not (self.fused_out and l is self.layers[-1])] +
                      [(l.dgrad, params[l.conv_prefix + ".weight"]) for l in self.layers
                       if l._bwd_ready and getattr(l, "dgrad", None) is not None and l.f8_dgrad is None])
-        O.ncdhw_to_cl(x.contiguous(), self.x0, self.dtype)
-        if training:
+        if ctp is not None:
             s0 = self.layers[0].in_sums
-            per = s0.numel() // self.G
-            for gi in range(self.G):                  # statistics of the stack input, per pass
-                O.bn_stats(self.x0[gi * self.gb:(gi + 1) * self.gb], self.dtype, s0[gi * per:(gi + 1) * per])
+            ctp.fill(self.x0, self.dtype, s0 if training else None, s0.numel() // self.G, STATS_NREP)
+        else:
+            O.ncdhw_to_cl(x.contiguous(), self.x0, self.dtype)
+            if training:
+                s0 = self.layers[0].in_sums
+                per = s0.numel() // self.G
+                for gi in range(self.G):                  # statistics of the stack input, per pass
+                    O.bn_stats(self.x0[gi * self.gb:(gi + 1) * self.gb], self.dtype, s0[gi * per:(gi + 1) * per])
         h = self.x0
         out = torch.empty((self.batch, self.cout) + self.out_dims, dtype=torch.float32, device=self.device)
         for i, lay in enumerate(self.layers):
@@ -175,7 +186,7 @@ class StackContext:
             c = lay.conv_prefix
             if not lay.fold:
                 lay.fwd.prep(params[c + ".weight"], params[c + ".bias"])
-            if with_bwd:
+            if with_bwd and not (self.fused_out and lay is self.layers[-1]):       # (its backward is _out_backward: no tables)
                 lay._init_bwd()
                 if getattr(lay, "dgrad", None) is not None and lay.f8_dgrad is None:
                     lay.dgrad.prep(params[c + ".weight"])
@@ -237,6 +248,22 @@ class StackContext:
                 O.cl_to_ncdhw(self._dx, dx, dt)
                 return dx
         return None
+
+
+class CtpInput:
+    """The stack input of one CTP-conditioned encoder call (common/model/Cae3D.Enc3DCtp): per pass a shape label
+    (B, 1, D, H, W) fp32 with contiguous spatial dimensions and any batch stride, and the padded CBV / TTD volumes
+    (B, 1, Dp, Hp, Wp) shared by all passes, cropped at ``offsets`` (D, H, W) to the label's extent."""
+
+    def __init__(self, labels, cbv, ttd, offsets):
+        self.labels, self.cbv, self.ttd, self.offsets = list(labels), cbv, ttd, tuple(offsets)
+
+    def with_labels(self, labels):
+        return CtpInput(labels, self.cbv, self.ttd, self.offsets)
+
+    def fill(self, x0, dtype, sums, sums_gstride, nrep):
+        """x0 = the channels-last stack input of every pass; sums (training): the first layer's accumulator"""
+        O.ctp_stack_input(self.labels, self.cbv, self.ttd, self.offsets, x0, dtype, sums, sums_gstride, nrep)
 
 
 class StackPool:

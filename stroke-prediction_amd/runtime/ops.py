@@ -916,6 +916,27 @@ def ncdhw_to_cl(src, dst, dtype):
     L.call("sp_ncdhw_to_cl", ptr(src), ptr(dst), dtype, B, Cc, dhw, dst.shape[-1], stream())
 
 
+def ctp_stack_input(labels, cbv, ttd, offsets, dst, dtype, sums=None, sums_gstride=0, nrep=0):
+    """Stack input of a CTP-conditioned encoder call (csrc/sp_ctp.hip): dst[g B + b] = channels-last (labels[g], CBV, TTD, 0, ...)
+    with CBV / TTD = cbv / ttd (B, 1, Dp, Hp, Wp) cropped at ``offsets`` (D, H, W) to the labels' extent.  labels: G fp32 tensors
+    (B, 1, D, H, W) with contiguous spatial dimensions and any batch stride (``labels[:, k:k+1]`` views).  sums (training): the
+    first layer's accumulator, G regions of ``sums_gstride`` doubles with ``nrep`` replica rows each; None: no statistics."""
+    G = len(labels)
+    B, _, D, H, W = labels[0].shape
+    for t in list(labels) + [cbv, ttd]:
+        assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 5 and t.shape[:2] == (B, 1), (t.dtype, tuple(t.shape))
+        assert t.stride()[2:] == (t.shape[3] * t.shape[4], t.shape[4], 1), "spatial dimensions must be contiguous"
+    assert all(tuple(t.shape) == (B, 1, D, H, W) for t in labels) and cbv.shape == ttd.shape
+    assert tuple(dst.shape[:4]) == (G * B, D, H, W) and dst.is_contiguous() and dst.dtype == TORCH_DT[dtype]
+    assert sums is None or (sums.dtype == torch.float64 and sums.numel() >= G * sums_gstride)
+    Dp, Hp, Wp = cbv.shape[2:]
+    ptrs = (C.c_void_p * G)(*[t.data_ptr() for t in labels])
+    bstr = (C.c_int64 * G)(*[t.stride(0) for t in labels])
+    L.call("sp_ctp_stack_input", ptrs, bstr, G, B, D, H, W, ptr(cbv), cbv.stride(0), ptr(ttd), ttd.stride(0), Dp, Hp, Wp,
+           int(offsets[0]), int(offsets[1]), int(offsets[2]), ptr(dst), dtype, dst.shape[-1], ptr(sums), int(sums_gstride),
+           int(nrep), stream())
+
+
 def cl_to_ncdhw(src, dst, dtype):
     B, Cc = dst.shape[:2]
     dhw = int(np.prod(dst.shape[2:]))
