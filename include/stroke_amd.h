@@ -880,6 +880,47 @@ int sp_map_coordinates_linear(const float* image, const float* d0, const float* 
 int sp_surface_distances(const float* result, const float* reference, float threshold, int32_t ndim, const int32_t* dims,
                          float* ws, double* out, sp_stream_t stream);
 
+/* ------------------------------------------------------------------ signed-distance-map baseline (csrc/sp_sdm.hip)
+ * test_sdm_resampling.py:15-52 of the reference (sdm_interpolate_numpy) on the device, in fp64.  Volumes are C-ordered
+ * (D, H, W).  Dtype codes of the zoom's source / output and of the blend's t: */
+enum { SP_SDM_F64 = 0, SP_SDM_I8 = 1,
+       SP_SDM_F32_AS_I8 = 2,   /* source: fp32 converted to int8 first (numpy astype(int8), truncation) */
+       SP_SDM_MASK_GT0 = 3,    /* output: fp32 1 where the zoomed value is > 0, else 0 */
+       SP_SDM_MASK_LT0 = 4,    /* output: fp32 1 where the zoomed value is < 0, else 0 */
+       SP_SDM_F32 = 5 };       /* t: fp32 values; (1 - t) is then rounded in fp32, as numpy does for a float32 scalar */
+/* the info record (int32[8], device memory) that sp_sdm_signed_fields writes */
+enum { SP_SDM_INFO_ARTIFICIAL = 0, SP_SDM_INFO_COG = 1 /* 3 entries, -1 without artificial core */, SP_SDM_INFO_DEGENERATE = 4 };
+/* planning, host only: latent extents ext[0..2] = (D, round(H / zoom), round(W / zoom)) and recon extents ext[3..5] -- with
+ * resample the [2:130] crop of the zoom-by-zoom upsampled latents (numpy slice semantics), else (D, H, W) -- and the bytes
+ * of ONE workspace that serves every sp_sdm_* call of an interpolation with T values of t (the calls are stream-ordered). */
+int sp_sdm_plan(int32_t D, int32_t H, int32_t W, double zoom, int32_t resample, int32_t T, int32_t* ext, int64_t* ws_bytes);
+/* core_dist = edt(1 - core_bin) - edt(core > thr), penu_dist = edt(penu > thr) - edt(penu < thr) (fp64, D*H*W each), edt =
+ * scipy.ndimage.distance_transform_edt with unit spacing: the four seed masks, then the four separable transforms in the same
+ * three launches (exact integer squared distances, roots in fp64).  core_bin = core > thr; if it is empty and the penumbra
+ * mask is not, the voxel int(center_of_mass(penu > thr)) dilated by `dilate` (>= 1) iterations of the cross (the L1 ball,
+ * clipped) -- decided on the device.  info (int32[8]): [0] artificial core applied, [1..3] its cog, [4] bit k set when
+ * transform k (penu > thr, penu < thr, 1 - core_bin, core > thr) has no zero voxel (its result is meaningless), [5..7] 0.
+ * ws: at least the bytes of sp_sdm_plan. */
+int sp_sdm_signed_fields(const float* core, const float* penu, int32_t D, int32_t H, int32_t W, float threshold, int32_t dilate,
+                         double* core_dist, double* penu_dist, int32_t* info, void* ws, int64_t ws_bytes, sp_stream_t stream);
+/* host only: the full output extents round(in * factor) of scipy.ndimage.zoom and the workspace bytes of sp_sdm_zoom for a
+ * batch of `batch` volumes of rank ndim <= 3 */
+int sp_sdm_zoom_plan(int32_t ndim, const int32_t* in_dims, const double* factors, int32_t batch, int32_t* full_dims, int64_t* ws_bytes);
+/* scipy.ndimage.zoom(x, factors, order=3, mode="constant", grid_mode=False) of each of `batch` volumes stored back to back:
+ * the cubic B-spline prefilter with mirror boundaries along every axis that changes extent (an axis that keeps it is sampled
+ * at the knots and skipped), then a separable 4-tap evaluation with mirrored coefficient indices, output index o of an axis
+ * reading coordinate o (n_in - 1) / (n_full - 1).  Only the window [crop_lo, crop_lo + crop_n) of the full output is written
+ * (null: all of it); an axis that keeps its extent takes no crop.  src_dtype: SP_SDM_F64, SP_SDM_I8, SP_SDM_F32_AS_I8;
+ * dst_dtype: SP_SDM_F64, SP_SDM_I8 (scipy's rounding: half away from zero), SP_SDM_MASK_GT0 / _LT0.  A contiguous axis
+ * that changes extent has at most 256 samples.  in_dims, full_dims, crop_*: host arrays; ws: sp_sdm_zoom_plan's bytes. */
+int sp_sdm_zoom(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int32_t batch, int32_t ndim, const int32_t* in_dims,
+                const int32_t* full_dims, const int32_t* crop_lo, const int32_t* crop_n, void* ws, int64_t ws_bytes, sp_stream_t stream);
+/* intp[k][i] = penu[i] * t_k - core[i] * (1 - t_k) for the T device values t (t_dtype SP_SDM_F64 or SP_SDM_F32), fp64 without
+ * contraction.  Exactly one of intp_out (write the blend) and intp_in (T x n values given: masks only) is set.  masks
+ * (optional, fp32 (T + 2) x n): [k] = intp_k > 0, [T] = core < 0, [T + 1] = penu > 0. */
+int sp_sdm_blend(const double* penu, const double* core, const void* t, int32_t t_dtype, int32_t T, int64_t n, const double* intp_in,
+                 double* intp_out, float* masks, sp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

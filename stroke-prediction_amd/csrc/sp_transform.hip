@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "sp_common.h"
+#include "sp_edt.h"
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 #define SP_GAUSS_MAX_RADIUS 64
@@ -110,7 +111,6 @@ extern "C" int sp_map_coordinates_linear(const float* image, const float* d0, co
 // voxel apart.  All of that is reproduced: arrays of rank <= 5, unit spacing.
 // Exact EDT, separable: g <- min_j g[.., j, ..] + (i - j)^2 along each axis in turn.  With extents <= 128 the plain
 // O(n) scan per voxel is ~270 fused min-adds per voxel for 4 x 88^3 -- less than a millisecond, no lower-envelope stack.
-#define SP_SD_BIG 1.0e30f
 struct Dims5 { int n[5]; };
 
 __global__ __launch_bounds__(256) void sd_border_kernel(const float* __restrict__ x, float thr, Dims5 d, int a0, int64_t total,
@@ -139,20 +139,10 @@ __global__ __launch_bounds__(256) void sd_seed_kernel(const float* __restrict__ 
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx < total) g[idx] = border[idx] != 0.f ? 0.f : SP_SD_BIG;
 }
-// one axis: element (o, i, k) of an (outer, n, inner) view
+// one axis: element (o, i, k) of an (outer, n, inner) view (the scan itself: sp_edt.h)
 __global__ __launch_bounds__(256) void sd_edt_axis_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t total, int n,
                                                           int64_t inner) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int64_t k = idx % inner, oi = idx / inner;
-  const int i = (int)(oi % n);
-  const float* line = src + (oi - i) * inner + k;
-  float best = SP_SD_BIG;
-  for (int j = 0; j < n; ++j) {
-    const float dj = (float)(i - j);
-    best = fminf(best, fmaf(dj, dj, line[(int64_t)j * inner]));
-  }
-  dst[idx] = best;
+  sp_edt_axis(src, dst, total, n, inner);
 }
 // out[0] = max of g (the SQUARED distance: an exact integer, the host takes the root in double), out[1] = sum of sqrt(g)
 // in double, out[2] = count, over the voxels where `at` is set

@@ -12,7 +12,7 @@ PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("SP_LIB_PATH") or os.path.join(PKG_DIR, "lib", "libstroke_amd.so")   # SP_LIB_PATH: diagnostic builds (tools/)
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
 SOURCES = ["sp_conv.hip", "sp_conv_dma.hip", "sp_conv_par.hip", "sp_conv_zm.hip", "sp_conv_zm8.hip", "sp_wgrad.hip", "sp_wgrad_dma.hip", "sp_conv_fc.hip", "sp_wgrad_zr.hip", "sp_wgrad_pw.hip", "sp_wgrad_f8.hip", "sp_plan.hip", "sp_comm.hip", "sp_head.hip", "sp_first.hip", "sp_elem.hip", "sp_pwout.hip",
-           "sp_transform.hip", "sp_ctp.hip"]
+           "sp_transform.hip", "sp_ctp.hip", "sp_sdm.hip"]
 
 SP_BF16, SP_F32, SP_HL = 0, 1, 2      # SP_HL: bf16 pair (hi + lo tensors), the forward storage of the "bf16x3" mode
 # precision modes of the models (``Unet3D(dtype=...)``, ``Enc3D(dtype=...)``) -> storage type of the engine's tensors
@@ -112,6 +112,11 @@ _SIGS = {
     "sp_surface_distances": ([vp, vp, f32, i32, vp, vp, vp, vp], i32),
     "sp_gaussian_filter3d": ([vp, vp, vp, i32, i32, i32, f32, f32, vp], i32),
     "sp_map_coordinates_linear": ([vp, vp, vp, vp, f32, f32, f32, f32, vp, i32, i32, i32, vp], i32),
+    "sp_sdm_plan": ([i32, i32, i32, f64, i32, i32, vp, vp], i32),
+    "sp_sdm_signed_fields": ([vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, i64, vp], i32),
+    "sp_sdm_zoom_plan": ([i32, vp, vp, i32, vp, vp], i32),
+    "sp_sdm_zoom": ([vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp], i32),
+    "sp_sdm_blend": ([vp, vp, vp, i32, i32, i64, vp, vp, vp, vp], i32),
     "sp_conv_prep_weights_batch": ([vp, i32, i32, vp], i32),
     "sp_conv3d_igemm": ([C.POINTER(ConvArgs), vp], i32),
     "sp_conv3d_igemm_multi": ([C.POINTER(ConvArgs), i32, vp], i32),
@@ -312,7 +317,7 @@ def build(verbose=False):
     import subprocess
     os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
     srcs = [os.path.join(CSRC_DIR, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC_DIR, "sp_common.h"), os.path.join(os.path.dirname(PKG_DIR), "include", "stroke_amd.h")]
+    hdrs = [os.path.join(CSRC_DIR, "sp_common.h"), os.path.join(CSRC_DIR, "sp_edt.h"), os.path.join(os.path.dirname(PKG_DIR), "include", "stroke_amd.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     jobs, links = [], []
     for variant, (fname, flags) in VARIANTS.items():
