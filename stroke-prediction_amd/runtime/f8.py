@@ -35,9 +35,7 @@ WGRAD_ONLY = bool(int(os.environ.get("SP_F8_WGRAD_ONLY", "1")))  # ... and those
 DZ_FMT = E5M2 if os.environ.get("SP_F8_DZ", "e5m2") == "e5m2" else E4M3      # storage format of the quantised output gradients
 
 
-_F8_ITEM = np.dtype([("w", "<u8"), ("sCo", "<i8"), ("sCi", "<i8"), ("Cout", "<i4"), ("Cin", "<i4"), ("kmap", "<u8"), ("nsteps", "<i4"), ("NT", "<i4"),
-                     ("wfrag", "<u8"), ("fold_scale", "<u8"), ("fold_shift", "<u8"), ("bias", "<u8"), ("bias_out", "<u8"), ("winv", "<u8"),
-                     ("ntaps", "<i4"), ("out_scale", "<f4")])      # sp_f8_prep_item
+_F8_ITEM = np.dtype(L.F8PrepItem)      # sp_f8_prep_item, filled from positional tuples
 _tables = {}
 
 

@@ -1,4 +1,8 @@
-"""ctypes binding of ``libstroke_amd.so`` (the C ABI in ``include/stroke_amd.h``).
+"""ctypes binding of ``libstroke_amd.so``, derived from the one definition of its C ABI, ``include/stroke_amd.h``.
+
+The header is read once at import (``parse_header``): every ``typedef struct`` becomes a ``ctypes.Structure``, every declared
+function gets its ``argtypes`` / ``restype``, every ``enum`` constant its value.  An entry point added to the header and to a
+``.hip`` file is callable with no edit here; a declaration the parser does not understand raises at import.
 
 The library is built in-tree by ``__graft_entry__.build()`` (``hipcc
 --offload-arch=gfx950``).  There is no fallback: if it is missing or a call
@@ -6,15 +10,91 @@ fails, a ``RuntimeError`` carrying ``sp_last_error`` is raised.
 """
 import ctypes as C
 import os
+import re
+import threading as _threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("SP_LIB_PATH") or os.path.join(PKG_DIR, "lib", "libstroke_amd.so")   # SP_LIB_PATH: diagnostic builds (tools/)
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
+HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "stroke_amd.h")
 SOURCES = ["sp_conv.hip", "sp_conv_dma.hip", "sp_conv_par.hip", "sp_conv_zm.hip", "sp_conv_zm8.hip", "sp_wgrad.hip", "sp_wgrad_dma.hip", "sp_conv_fc.hip", "sp_wgrad_zr.hip", "sp_wgrad_pw.hip", "sp_wgrad_f8.hip", "sp_plan.hip", "sp_comm.hip", "sp_head.hip", "sp_first.hip", "sp_elem.hip", "sp_pwout.hip",
            "sp_transform.hip", "sp_ctp.hip", "sp_sdm.hip"]
 
-SP_BF16, SP_F32, SP_HL = 0, 1, 2      # SP_HL: bf16 pair (hi + lo tensors), the forward storage of the "bf16x3" mode
+i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
+_POINTEES = {"void", "char", "unsigned long long"}      # what the header names behind a `*` only
+_STATEMENT = re.compile(r"\s*((?:[^;{}]|\{[^{}]*\})+?)\s*;")      # up to the next `;` outside braces
+
+
+def parse_header(text):
+    """The declarations of a C header written like ``stroke_amd.h`` -> (structs, sigs, consts): a ``ctypes.Structure`` per struct
+    typedef, ``(argtypes, restype)`` per function, the value per enum constant.  ``int`` / ``int32_t`` -> ``c_int32``, ``int64_t``,
+    ``float``, ``double``, ``size_t`` -> their ctypes, every pointer -> ``c_void_p`` (which takes ``byref(...)``, ctypes arrays, raw
+    device addresses and ``None``).  Comments and preprocessor lines are dropped; what remains must be typedefs of structs or of
+    known types, anonymous enums of ``NAME = integer`` entries and function declarations: anything else raises ``ValueError``
+    with the offending text."""
+    types = {"int": i32, "int32_t": i32, "int64_t": i64, "float": f32, "double": f64, "size_t": C.c_size_t}
+    structs, sigs, consts = {}, {}, {}
+
+    def fail(what, decl):
+        raise ValueError("stroke_amd.h: %s in `%s`" % (what, " ".join(decl.split())[:160]))
+
+    def ctype(spec, decl):           # "const float*" -> c_void_p, "int32_t" -> c_int32, "sp_bn_bwd_args" -> that Structure
+        spec = re.sub(r"\bconst\b", " ", spec)
+        base = " ".join(spec.replace("*", " ").split())
+        if base not in types and not ("*" in spec and base in _POINTEES):
+            fail("unknown type `%s`" % base, decl)
+        return vp if "*" in spec else types[base]
+
+    def declarator(item, decl):      # "const float* gamma" -> ("const float*", "gamma")
+        m = re.fullmatch(r"\s*([^()]*[\s*])(\w+)\s*", item)
+        return m.groups() if m else fail("no `type name` in `%s`" % item.strip(), decl)
+
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)      # extern "C" { and its }
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    pos = 0
+    while text[pos:].strip():
+        m = _STATEMENT.match(text, pos)
+        if not m:
+            fail("unterminated declaration", text[pos:])
+        decl, pos = m.group(1), m.end()
+        if (m := re.fullmatch(r"typedef\s+struct\s+\w*\s*\{(.*)\}\s*(\w+)", decl, re.S)):
+            fields = []
+            for member in filter(str.strip, m.group(1).split(";")):
+                first, *more = member.split(",")                   # "int32_t B, Di, Hi": one type, three fields
+                spec, name = declarator(first, decl)
+                if not all(re.fullmatch(r"\s*\w+\s*", n) for n in more):
+                    fail("declarators of `%s`" % member.strip(), decl)
+                fields += [(n.strip(), ctype(spec, decl)) for n in [name] + more]
+            types[m.group(2)] = structs[m.group(2)] = type(m.group(2), (C.Structure,), {"_fields_": fields})
+        elif (m := re.fullmatch(r"typedef\s(.*)", decl, re.S)):
+            spec, name = declarator(m.group(1), decl)
+            types[name] = ctype(spec, decl)
+        elif (m := re.fullmatch(r"enum\s*\{(.*)\}", decl, re.S)):
+            for entry in filter(str.strip, m.group(1).split(",")):
+                e = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", entry) or fail("enum entry `%s` is not NAME = integer" % entry.strip(), decl)
+                consts[e.group(1)] = int(e.group(2))
+        elif (m := re.fullmatch(r"([^()]*)\(([^()]*)\)", decl, re.S)):
+            ret, name = declarator(m.group(1), decl)
+            params = [] if m.group(2).strip() == "void" else m.group(2).split(",")
+            sigs[name] = ([ctype(declarator(p, decl)[0], decl) for p in params], None if ret.strip() == "void" else ctype(ret, decl))
+        else:
+            fail("neither typedef, enum nor function", decl)
+    return structs, sigs, consts
+
+
+with open(HEADER) as _f:
+    STRUCTS, SIGS, CONSTS = parse_header(_f.read())
+EXPORTS = sorted(SIGS)
+BnFinArgs, BnBwdArgs, ConvArgs, WgradArgs, WgradF8Args, ConvFcArgs, Conv3dDesc, Conv3dPlan, Conv3dWgradPlan, PrepItem, F8PrepItem = (
+    STRUCTS[n] for n in ("sp_bn_fin_args", "sp_bn_bwd_args", "sp_conv_args", "sp_wgrad_args", "sp_wgrad_f8_args", "sp_conv_fc_args",
+                         "sp_conv3d_desc", "sp_conv3d_plan_t", "sp_conv3d_wgrad_plan_t", "sp_prep_item", "sp_f8_prep_item"))
+# SP_HL: bf16 pair (hi + lo tensors), the forward storage of the "bf16x3" mode; SP_REDUCE_ROWS: replica rows of the accumulators
+# the elementwise kernels reduce into
+SP_BF16, SP_F32, SP_HL, SP_REDUCE_ROWS = (CONSTS[n] for n in ("SP_BF16", "SP_F32", "SP_HL", "SP_REDUCE_ROWS"))
+ACT_NONE, ACT_LEAKY, ACT_ELU, ACT_SIGMOID = (CONSTS["SP_ACT_" + n] for n in ("NONE", "LEAKY", "ELU", "SIGMOID"))
+
 # precision modes of the models (``Unet3D(dtype=...)``, ``Enc3D(dtype=...)``) -> storage type of the engine's tensors
 DTYPE_CODES = {"bf16": SP_BF16, "f32": SP_F32, "fp8": SP_BF16, "fp8b": SP_BF16, "f16": SP_BF16, "bf16x3": SP_BF16, "f16x3": SP_BF16}
 #   fp8: bf16 storage + fp8 MFMA operands (runtime/f8.py); fp8b: the bf16 forward with the fp8 BACKWARD (data and weight
@@ -26,201 +106,8 @@ DTYPE_CODES = {"bf16": SP_BF16, "f32": SP_F32, "fp8": SP_BF16, "fp8b": SP_BF16, 
 #   f16x3: the same in the IEEE-half build (pairs of halves: ~22 bits forward; the backward is the f16 mode's, 8x closer than bf16)
 VARIANTS = {"": ("libstroke_amd.so", []), "f16": ("libstroke_amd_f16.so", ["-DSP_HALF_F16"])}
 VARIANT_OF = {"bf16": "", "f32": "", "fp8": "", "fp8b": "", "f16": "f16", "bf16x3": "", "f16x3": "f16"}
-SP_REDUCE_ROWS = 8    # replica rows of the accumulators the elementwise kernels reduce into (include/stroke_amd.h)
-ACT_NONE, ACT_LEAKY, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3
 
-i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
-
-
-class BnFinArgs(C.Structure):      # sp_bn_fin_args
-    _fields_ = [(n, vp) for n in ("sums", "gamma", "beta", "running_mean", "running_var", "scale", "shift", "mean", "invstd")] + \
-               [("count", f64), ("momentum", f32), ("eps", f32), ("nrep", i32), ("training", i32), ("C", i32), ("CP", i32)]
-
-
-class BnBwdArgs(C.Structure):      # sp_bn_bwd_args
-    _fields_ = [(n, vp) for n in ("sums", "gamma", "mean", "invstd", "dgamma", "dbeta", "coef")] + \
-               [("count", f64), ("pscale", f32), ("nrep", i32), ("C", i32), ("CP", i32)]
-
-
-class ConvArgs(C.Structure):
-    _fields_ = [(n, vp) for n in ("x", "y", "wfrag_hi", "wfrag_lo", "in_scale", "in_shift", "bias", "stats", "ktab")] + \
-               [(n, i32) for n in (
-                   "dtype_in", "dtype_out", "B", "Di", "Hi", "Wi", "CPi", "Do", "Ho", "Wo", "YD", "YH", "YW", "CPo",
-                   "osD", "osH", "osW", "ooD", "ooH", "ooW", "Cout", "sD", "sH", "sW", "o0D", "o0H", "o0W",
-                   "TD", "TH", "ITD", "ITH", "ITW", "MT", "NT", "NTtot", "ngroups", "octs_per_group", "opp", "vsb",
-                   "plane_bytes", "lo_offset", "steps_per_group", "lds_bytes", "act")] + [("act_param", f32), ("dma", i32), ("zfill", i32), ("persist", i32), ("aux", vp), ("stats_mode", i32), ("stats_nrep", i32), ("ITH_zs", i32), ("x_plane", i64),
-                                                                           ("y8", vp), ("y8_plane", i64), ("f8_wscale", vp), ("y8_scale", f32), ("f8_bin", i32),
-                                                                           ("group_batch", i32), ("nslices", i32),
-                                                                          ("slice_wfrag_stride", i64), ("x_lo_delta", i64), ("y_lo_delta", i64),
-                                                                          ("bias_tab", vp), ("bias_tab_gstride", i32), ("pad_", i32), ("wfrag_gstride", i64),
-                                                                          ("bnb", BnBwdArgs), ("dz_sums", vp), ("pool_y", vp), ("pool_lo_delta", i64), ("y2", vp), ("split_nt", i32), ("CPo2", i32), ("pser_planes", i32), ("pad2_", i32)]
-
-
-class WgradArgs(C.Structure):
-    _fields_ = [(n, vp) for n in ("x", "dz", "in_scale", "in_shift", "dz_scale", "dz_shift", "dw_acc", "taps")] + \
-               [(n, i32) for n in ("dtype", "B", "Di", "Hi", "Wi", "CPi", "Do", "Ho", "Wo", "CPo", "sD", "sH", "sW",
-                                   "o0D", "o0H", "o0W", "ntap", "kD", "kH", "kW", "CoT", "CiT", "nblocks", "dma", "tile_rows", "parts", "cib")] + [("x_plane", i64), ("zs", i32), ("groups", i32)]
-
-
-class WgradF8Args(C.Structure):      # sp_wgrad_f8_args
-    _fields_ = [(n, vp) for n in ("x", "dz", "dw_acc")] + \
-               [(n, i32) for n in ("B", "Di", "Hi", "Wi", "Do", "Ho", "Wo", "CoT", "CiT", "nblocks")] + [("x_plane", i64), ("dz_plane", i64)]
-
-
-class ConvFcArgs(C.Structure):       # sp_conv_fc_args
-    _fields_ = [(n, vp) for n in ("x", "y", "wfrag", "in_scale", "in_shift", "bias", "stats", "aux", "partial", "taps")] + \
-               [(n, i32) for n in ("B", "Di", "Hi", "Wi", "CPi", "Do", "Ho", "Wo", "CPo", "Cout", "sD", "sH", "sW", "o0D", "o0H", "o0W",
-                                   "ntap", "act")] + [("act_param", f32), ("stats_mode", i32), ("stats_nrep", i32), ("dtype_out", i32), ("x_plane", i64),
-                                                                         ("group_batch", i32), ("coef_gstride", i32)]
-
-
-class Conv3dDesc(C.Structure):       # sp_conv3d_desc
-    _fields_ = [(n, i32) for n in ("B", "Cin", "Cout", "D", "H", "W", "grad", "padD", "padH", "padW", "transposed")]
-
-
-class Conv3dPlan(C.Structure):       # sp_conv3d_plan_t
-    _fields_ = [(n, i32) for n in ("cin_op", "cout_op", "P", "NT", "MT", "NW", "NSLOT", "KS", "nsteps", "ITH",
-                                   "Di", "Hi", "Wi", "Do", "Ho", "Wo", "o0", "o0H", "o0W", "mirror")] + \
-               [(n, i64) for n in ("x_elems", "y_elems", "workspace_bytes", "off_zero", "off_ktab", "off_kmap", "off_bias", "off_wfrag")]
-
-
-class Conv3dWgradPlan(C.Structure):  # sp_conv3d_wgrad_plan_t
-    _fields_ = [(n, i32) for n in ("CoT", "CiT", "nblocks", "Do", "Ho", "Wo")] + \
-               [(n, i64) for n in ("workspace_bytes", "off_taps", "off_tapsrc", "off_acc")]
-
-
-_SIGS = {
-    "sp_conv_fc_workspace": ([i32, i32, i32, i32, i32, i32, C.POINTER(i64)], i32),
-    "sp_conv_fc": ([C.POINTER(ConvFcArgs), vp], i32),
-    "sp_conv3d_plan": ([C.POINTER(Conv3dDesc), C.POINTER(Conv3dPlan)], i32),
-    "sp_conv3d_tables": ([C.POINTER(Conv3dDesc), C.POINTER(Conv3dPlan), vp, vp], i32),
-    "sp_conv3d_init": ([C.POINTER(Conv3dDesc), C.POINTER(Conv3dPlan), vp, vp], i32),
-    "sp_conv3d_set_weights": ([C.POINTER(Conv3dDesc), C.POINTER(Conv3dPlan), vp, vp, vp, vp, vp, vp], i32),
-    "sp_conv3d_run": ([C.POINTER(Conv3dDesc), C.POINTER(Conv3dPlan), vp, vp, vp, i32, i32, f32, vp, i32, i64, vp], i32),
-    "sp_conv3d_wgrad_plan": ([C.POINTER(Conv3dDesc), C.POINTER(Conv3dWgradPlan)], i32),
-    "sp_conv3d_wgrad_init": ([C.POINTER(Conv3dDesc), C.POINTER(Conv3dWgradPlan), vp, vp], i32),
-    "sp_conv3d_wgrad_run": ([C.POINTER(Conv3dDesc), C.POINTER(Conv3dWgradPlan), vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i64, vp], i32),
-    "sp_version": ([], i32),
-    "sp_comm_available": ([], i32),
-    "sp_comm_unique_id": ([vp], i32),
-    "sp_comm_init_rank": ([C.POINTER(vp), i32, vp, i32], i32),
-    "sp_comm_destroy": ([vp], i32),
-    "sp_allreduce_flat": ([vp, vp, i64, vp], i32),
-    "sp_allreduce_flat_f64": ([vp, vp, i64, vp], i32),
-    "sp_reduce_scatter_flat": ([vp, vp, i64, i32, vp], i32),
-    "sp_allgather_flat": ([vp, vp, i64, i32, vp], i32),
-    "sp_surface_distances": ([vp, vp, f32, i32, vp, vp, vp, vp], i32),
-    "sp_gaussian_filter3d": ([vp, vp, vp, i32, i32, i32, f32, f32, vp], i32),
-    "sp_map_coordinates_linear": ([vp, vp, vp, vp, f32, f32, f32, f32, vp, i32, i32, i32, vp], i32),
-    "sp_sdm_plan": ([i32, i32, i32, f64, i32, i32, vp, vp], i32),
-    "sp_sdm_signed_fields": ([vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, i64, vp], i32),
-    "sp_sdm_zoom_plan": ([i32, vp, vp, i32, vp, vp], i32),
-    "sp_sdm_zoom": ([vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp], i32),
-    "sp_sdm_blend": ([vp, vp, vp, i32, i32, i64, vp, vp, vp, vp], i32),
-    "sp_conv_prep_weights_batch": ([vp, i32, i32, vp], i32),
-    "sp_conv3d_igemm": ([C.POINTER(ConvArgs), vp], i32),
-    "sp_conv3d_igemm_multi": ([C.POINTER(ConvArgs), i32, vp], i32),
-    "sp_bn_act_bwd_groups_cls": ([vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, i32, i32, i32, i32, vp, vp], i32),
-    "sp_wgrad_finish_folded_groups": ([vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp], i32),
-    "sp_cae_loss_fwd": ([vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i32, i64, vp, vp, i64, f32, f64, f32, vp, vp, vp, vp], i32),
-    "sp_cae_loss_bwd": ([vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp], i32),
-    "sp_pwout_fwd": ([vp, i32, i64, i32, i32, vp, i32, i32, vp, vp, vp, vp], i32),
-    "sp_pwout_bwd": ([vp, vp, vp, i32, i64, i32, i32, vp, i32, i32, vp, vp, vp], i32),
-    "sp_pwout_finish": ([vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp], i32),
-    "sp_conv_prep_folded_groups": ([vp, i64, i64, i32, i32, vp, i32, i32, vp, i64, vp, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp], i32),
-    "sp_conv3d_par": ([C.POINTER(ConvArgs), i32, vp, C.POINTER(i32), vp, vp], i32),
-    "sp_conv3d_zm": ([C.POINTER(ConvArgs), vp, vp], i32),
-    "sp_conv3d_zm_config": ([i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], i32),
-    "sp_conv3d_zm_config_hl": ([i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], i32),
-    "sp_conv3d_zm_config_ps": ([i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], i32),
-    "sp_bn_stats_ncdhw_f32": ([vp, i32, i32, i64, i32, vp, i32, vp], i32),
-    "sp_first_prep_hl": ([vp, vp, vp, vp, vp, vp, vp, i32, vp], i32),
-    "sp_first_conv_fwd_hl": ([vp, i32, i32, i32, i32, vp, vp, vp, i32, f32, vp, vp, vp, i32, i32, vp], i32),
-    "sp_maxpool2_fwd_hl": ([vp, i64, vp, i64, i32, i32, i32, i32, i32, vp, vp], i32),
-    "sp_upsample2_crop_cat_fwd_hl": ([vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp, vp], i32),
-    "sp_head_fwd_hl": ([vp, i64, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, f32, vp, vp], i32),
-    "sp_conv3d_zm8": ([C.POINTER(ConvArgs), vp, vp], i32),
-    "sp_conv3d_zm8_config": ([i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], i32),
-    "sp_conv_prep_f8": ([vp, i64, i64, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, f32, vp], i32),
-    "sp_quantize_f8": ([vp, i32, i64, vp, i64, i64, i32, f32, vp], i32),
-    "sp_conv_prep_f8_batch": ([vp, i32, i32, vp], i32),
-    "sp_conv_prep_weights": ([vp, i64, i64, i32, i32, vp, i32, i32, vp, vp, vp, vp], i32),
-    "sp_conv_fold_bias": ([vp, i64, i64, i32, i32, i32, vp, vp, vp, i32, vp], i32),
-    "sp_conv_prep_folded": ([vp, i64, i64, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp], i32),
-    "sp_conv_prep_folded_bn": ([vp, i64, i64, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, C.POINTER(BnFinArgs), vp], i32),
-    "sp_first_prep_bn": ([vp, vp, vp, vp, vp, i32, C.POINTER(BnFinArgs), vp], i32),
-    "sp_conv3d_wgrad": ([C.POINTER(WgradArgs), vp], i32),
-    "sp_wgrad_finish": ([vp, i32, vp, i32, i32, i32, i32, i32, i64, i64, vp, vp, vp, i32, i32, vp], i32),
-    "sp_wgrad_finish_folded": ([vp, i32, vp, i32, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], i32),
-    "sp_wgrad_finish_folded_scaled": ([vp, i32, vp, i32, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp], i32),
-    "sp_conv3d_wgrad_f8": ([C.POINTER(WgradF8Args), vp], i32),
-    "sp_conv_partial_finish": ([vp, i32, i64, i32, vp, i32, i32, f32, vp, vp, i32, vp, i64, vp], i32),
-    "sp_upsample2_crop_cat_fwd": ([vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp, vp], i32),
-    "sp_confusion_counts": ([vp, vp, f32, i64, vp, vp], i32),
-    "sp_first_supported": ([i32, i32, i32], i32),
-    "sp_bn_stats_ncdhw": ([vp, i32, i32, i64, i32, vp, i32, vp], i32),
-    "sp_first_prep": ([vp, vp, vp, vp, vp, vp, vp], i32),
-    "sp_first_conv_fwd": ([vp, i32, i32, i32, i32, vp, vp, i32, f32, vp, vp, i32, vp], i32),
-    "sp_first_wgrad": ([vp, vp, i32, i32, i32, i32, vp, i32, vp], i32),
-    "sp_first_wgrad_fused": ([vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, i32, vp, vp], i32),
-    "sp_first_prep_n": ([vp, vp, vp, vp, vp, vp, i32, vp], i32),
-    "sp_first_conv_fwd_n": ([vp, i32, i32, i32, i32, vp, vp, i32, f32, vp, vp, i32, i32, vp, i64, vp], i32),
-    "sp_first_wgrad_n": ([vp, vp, i32, i32, i32, i32, vp, i32, i32, vp], i32),
-    "sp_first_wgrad_fused_n": ([vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, i32, vp, i32, vp], i32),
-    "sp_first_wgrad_fused_y8": ([vp, vp, vp, i64, vp, i32, f32, i32, i32, i32, i32, vp, i32, vp, i32, vp], i32),
-    "sp_ncdhw_to_cl": ([vp, vp, i32, i32, i32, i64, i32, vp], i32),
-    "sp_cl_to_ncdhw": ([vp, vp, i32, i32, i32, i64, i32, vp], i32),
-    "sp_ctp_stack_input": ([C.POINTER(vp), C.POINTER(i64), i32, i32, i32, i32, i32, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32,
-                            vp, i32, i32, vp, i64, i32, vp], i32),
-    "sp_bn_stats": ([vp, i32, i64, i32, vp, vp], i32),
-    "sp_bn_finalize": ([vp, i32, f64, vp, vp, vp, vp, f32, f32, i32, i32, i32, vp, vp, vp, vp, vp], i32),
-    "sp_bn_bwd_reduce": ([vp, vp, i32, i64, i32, vp, vp], i32),
-    "sp_bn_finalize_groups": ([vp, i32, f64, vp, vp, vp, vp, f32, f32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp], i32),
-    "sp_bn_bwd_finalize_groups": ([vp, i32, f64, vp, vp, vp, i32, i32, i32, vp, vp, vp, f32, vp], i32),
-    "sp_bn_act_bwd_groups": ([vp, vp, vp, i32, i64, i32, i32, f32, vp, vp, i64, vp], i32),
-    "sp_bn_bwd_finalize": ([vp, i32, f64, vp, vp, vp, i32, i32, vp, vp, vp, f32, vp], i32),
-    "sp_bn_act_bwd": ([vp, vp, vp, i32, i64, i32, i32, f32, vp, vp, vp], i32),
-    "sp_maxpool2_fwd": ([vp, vp, i32, i32, i32, i32, i32, i32, vp, vp], i32),
-    "sp_maxpool2_fwd_q8": ([vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i64, i32, f32, vp], i32),
-    "sp_bn_act_bwd_q8": ([vp, vp, vp, i32, i64, i32, i32, f32, vp, vp, vp, i64, i32, f32, vp], i32),
-    "sp_bn_act_bwd_y8": ([vp, vp, i64, vp, i64, i32, i32, f32, vp, vp, vp, i64, i32, f32, vp], i32),
-    "sp_maxpool2_fwd_x8": ([vp, i64, vp, i32, i32, i32, i32, i32, vp, vp, i64, i32, f32, vp], i32),
-    "sp_upsample2_crop_cat_fwd_q8s8": ([vp, i32, vp, i64, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp, vp, i64, i32, f32, vp], i32),
-    "sp_pool_skip_act_bwd_y8": ([vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, i64, i32, f32, vp], i32),
-    "sp_upsample2_crop_cat_fwd_q8": ([vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp, vp, i64, i32, f32, vp], i32),
-    "sp_pool_skip_act_bwd_q8": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
-                                 f32, vp, vp, vp, i64, i32, f32, vp], i32),
-    "sp_upsample2_fwd": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp], i32),
-    "sp_crop_copy": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], i32),
-    "sp_pool_skip_act_bwd": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
-                              f32, vp, vp, vp], i32),
-    "sp_upsample2_act_bwd": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp], i32),
-    "sp_upsample2_act_bwd_q8": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, i64, i32, f32, vp], i32),
-    "sp_out_grad_to_cl": ([vp, vp, i32, i32, i64, i32, i32, i32, f32, vp, vp, vp], i32),
-    "sp_dice_sums": ([vp, i64, vp, i64, i32, i32, i64, vp, vp], i32),
-    "sp_dice_finalize": ([vp, vp, f64, i32, vp, vp, vp], i32),
-    "sp_dice_finalize_clear": ([vp, vp, f64, i32, vp, vp, vp], i32),
-    "sp_dice_bwd": ([vp, i64, vp, i64, vp, vp, i32, i32, i64, vp, vp], i32),
-    "sp_head_supported": ([i32, i32, i32], i32),
-    "sp_head_supported_dtype": ([i32, i32, i32, i32], i32),
-    "sp_head_fwd": ([vp, i32, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, f32, vp, vp], i32),
-    "sp_head_bwd_rows": ([i64], i64),
-    "sp_head_row_floats": ([i32, i32, i32], i32),
-    "sp_head_bwd": ([vp, i32, i64, i32, i32, i32, vp, vp, i32, vp, i32, f32, vp, vp, i32, f32, vp, vp, vp], i32),
-    "sp_head_bwd_q8": ([vp, i32, i64, i32, i32, i32, vp, vp, i32, vp, i32, f32, vp, vp, i32, f32, vp, vp, vp, i64, i32, f32, vp], i32),
-    "sp_head_grad_finish": ([vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp], i32),
-    "sp_add_f64_to_f32": ([vp, vp, i64, f32, vp], i32),
-    "sp_axpby": ([vp, vp, vp, i32, i64, f32, f32, vp], i32),
-    "sp_lerp_batch": ([vp, vp, vp, vp, i32, i32, i64, vp], i32),
-    "sp_adam_step_flat": ([vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp], i32),
-    "sp_adam_step_flat_dev": ([vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp], i32),
-    "sp_adam_step_flat_hyp": ([vp, vp, vp, vp, i64, vp, vp, f32, vp], i32),
-}
-EXPORTS = sorted(list(_SIGS) + ["sp_last_error"])
-
-_lib = None
 _libs = {}
-import threading as _threading
 _tls = _threading.local()
 
 
@@ -253,43 +140,24 @@ def lib_path(variant=""):
 
 def load(variant=None):
     """Load the shared library (of the calling thread's current build, or the named one) once; raises if it has not been built."""
-    global _lib
     variant = current_variant() if variant is None else variant
-    if variant:
-        if variant in _libs:
-            return _libs[variant]
-        path = lib_path(variant)
+    lib = _libs.get(variant)
+    if lib is None:
+        # torch bundles its own HIP runtime (libamdhip64): import it FIRST so that this library binds to the
+        # same runtime instance (streams and device pointers are shared with torch); loading ours first would
+        # pull a second copy from /opt/rocm that never sees torch's context.
         import torch  # noqa: F401
+        path = lib_path(variant)
         if not os.path.exists(path):
-            raise RuntimeError("stroke_prediction_amd: %s is missing -- build it with `python -c \"import __graft_entry__ as g; "
-                               "g.build()\"`. There is no CPU/PyTorch fallback." % path)
+            raise RuntimeError(
+                "stroke_prediction_amd: %s is missing -- build it with `python -c \"import __graft_entry__ as g; "
+                "g.build()\"` (hipcc --offload-arch=gfx950). There is no CPU/PyTorch fallback." % path)
         lib = C.CDLL(path)
-        for name, (argtypes, restype) in _SIGS.items():
+        for name, (argtypes, restype) in SIGS.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype
-        lib.sp_last_error.argtypes = [C.c_char_p, C.c_size_t]
-        lib.sp_last_error.restype = None
         _libs[variant] = lib
-        return lib
-    if _lib is not None:
-        return _lib
-    # torch bundles its own HIP runtime (libamdhip64): import it FIRST so that this library binds to the
-    # same runtime instance (streams and device pointers are shared with torch); loading ours first would
-    # pull a second copy from /opt/rocm that never sees torch's context.
-    import torch  # noqa: F401
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "stroke_prediction_amd: %s is missing -- build it with `python -c \"import __graft_entry__ as g; "
-            "g.build()\"` (hipcc --offload-arch=gfx950). There is no CPU/PyTorch fallback." % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = restype
-    lib.sp_last_error.argtypes = [C.c_char_p, C.c_size_t]
-    lib.sp_last_error.restype = None
-    _lib = lib
     return lib
 
 
@@ -317,7 +185,7 @@ def build(verbose=False):
     import subprocess
     os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
     srcs = [os.path.join(CSRC_DIR, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC_DIR, "sp_common.h"), os.path.join(CSRC_DIR, "sp_edt.h"), os.path.join(os.path.dirname(PKG_DIR), "include", "stroke_amd.h")]
+    hdrs = [os.path.join(CSRC_DIR, "sp_common.h"), os.path.join(CSRC_DIR, "sp_edt.h"), HEADER]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     jobs, links = [], []
     for variant, (fname, flags) in VARIANTS.items():
@@ -345,8 +213,6 @@ def build(verbose=False):
             raise subprocess.CalledProcessError(pr.returncode, cmd)
     for cmd in links:
         subprocess.run(cmd, check=True)
-    global _lib
     if links:
-        _lib = None
         _libs.clear()
     return LIB_PATH

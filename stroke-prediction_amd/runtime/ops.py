@@ -831,9 +831,7 @@ class WgradRunner:
                    ptr(dbias_grad), nbias, _dbias_stride(dbias_sums), st)
 
 
-_PREP_ITEM = np.dtype([("w", "<u8"), ("sCo", "<i8"), ("sCi", "<i8"), ("Cout", "<i4"), ("Cin", "<i4"), ("kmap", "<u8"),
-                       ("nsteps", "<i4"), ("NTtot", "<i4"), ("hi", "<u8"), ("lo", "<u8"), ("fold", "<u8"),
-                       ("bias", "<u8"), ("bias_out", "<u8"), ("bias_n", "<i4"), ("bias_pad", "<i4")])   # sp_prep_item
+_PREP_ITEM = np.dtype(L.PrepItem)      # sp_prep_item, filled from positional tuples
 _prep_tables = {}
 
 

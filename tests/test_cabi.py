@@ -24,6 +24,65 @@ def test_library_exports_every_declared_symbol():
     assert sorted(names) == L.EXPORTS, (sorted(set(names) ^ set(L.EXPORTS)))
 
 
+def test_derived_struct_layouts_match_the_c_compiler(tmp_path):
+    """runtime/lib.py derives its ctypes structures from the header; the C compiler is the authority on padding: every sizeof and
+    every field offset of the derived classes, nested members included, holds as a _Static_assert against stroke_amd.h"""
+    import subprocess
+    assert sorted(L.STRUCTS) == sorted(re.findall(r"\}\s*(\w+)\s*;", re.sub(r"/\*.*?\*/", "", open(L.HEADER).read(), flags=re.S))) and len(L.STRUCTS) == 11
+    lines = ['#include "stroke_amd.h"']
+    for cname, T in L.STRUCTS.items():
+        lines.append("_Static_assert(sizeof(%s) == %d, \"sizeof %s\");" % (cname, ctypes.sizeof(T), cname))
+        for field, _ in T._fields_:
+            lines.append("_Static_assert(offsetof(%s, %s) == %d, \"%s.%s\");" % (cname, field, getattr(T, field).offset, cname, field))
+    assert len(lines) > 11 + 250
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "c", "-std=c11", "-fsyntax-only", "-I", os.path.dirname(L.HEADER), str(src)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert L.ConvArgs is L.STRUCTS["sp_conv_args"] and dict(L.ConvArgs._fields_)["bnb"] is L.BnBwdArgs
+
+
+def test_parser_refuses_what_it_does_not_understand():
+    """a declaration outside the header's small grammar raises with the offending text: nothing is skipped or guessed"""
+    import pytest
+    ok = "typedef void* sp_stream_t;\ntypedef struct s { const float* p; int32_t a, b; } s;\nenum { X = 3 };\nint64_t sp_f(const s* a, double d, sp_stream_t st);\n"
+    structs, sigs, consts = L.parse_header(ok)
+    assert [n for n, _ in structs["s"]._fields_] == ["p", "a", "b"] and consts == {"X": 3}
+    assert sigs == {"sp_f": ([L.vp, L.f64, L.vp], L.i64)}
+    for bad, named in (("int sp_g(uint16_t n);", "uint16_t"),                                    # unknown type name
+                       ("int sp_g(const sp_missing_args* a);", "sp_missing_args"),              # ... behind a pointer too
+                       ("typedef struct t { int32_t a; float b;\nint sp_g(void);", "struct t"),  # unterminated struct
+                       ("typedef struct t { int32_t a[4]; } t;", "a[4]"),                       # array member
+                       ("typedef struct t { float *a, *b; } t;", "*b"),                         # mixed declarators
+                       ("int sp_g(int32_t);", "int32_t"),                                       # unnamed parameter
+                       ("enum { A, B };", "A"),                                                 # enum entry without a value
+                       ("int sp_g(void (*cb)(int), int n);", "cb"),                             # function pointer
+                       ("int sp_g(int n)", "sp_g")):                                            # no terminating semicolon
+        with pytest.raises(ValueError, match=re.escape(named)):
+            L.parse_header(ok + bad)
+
+
+def test_every_declared_function_is_bound_with_its_parameter_count():
+    src = re.sub(r"/\*.*?\*/", "", open(L.HEADER).read(), flags=re.S)
+    decls = re.findall(r"\b(sp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src)
+    assert sorted(n for n, _ in decls) == _declared() == sorted(L.SIGS) and len(decls) >= 123
+    for name, params in decls:
+        want = 0 if params.strip() == "void" else params.count(",") + 1
+        assert len(L.SIGS[name][0]) == want, name
+    lib = L.load()
+    for name, (argtypes, restype) in L.SIGS.items():
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
+    assert L.SIGS["sp_head_bwd_rows"] == ([L.i64], L.i64)
+    assert L.SIGS["sp_head_row_floats"][1] is L.i32 and L.SIGS["sp_version"] == ([], L.i32)
+    assert L.SIGS["sp_last_error"] == ([L.vp, ctypes.c_size_t], None)
+    assert L.SIGS["sp_adam_step_flat"][0] == [L.vp] * 4 + [L.i64] + [L.f32] * 5 + [L.i32, L.f32, L.vp]
+    assert L.SIGS["sp_sdm_plan"][0] == [L.i32, L.i32, L.i32, L.f64, L.i32, L.i32, L.vp, L.vp]
+    assert (L.SP_BF16, L.SP_F32, L.SP_HL, L.SP_REDUCE_ROWS) == (0, 1, 2, 8)
+    assert (L.ACT_NONE, L.ACT_LEAKY, L.ACT_ELU, L.ACT_SIGMOID) == (0, 1, 2, 3)
+
+
 def test_version_and_error_text():
     lib = L.load()
     assert lib.sp_version() >= 100
