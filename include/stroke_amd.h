@@ -880,6 +880,21 @@ int sp_map_coordinates_linear(const float* image, const float* d0, const float* 
 int sp_surface_distances(const float* result, const float* reference, float threshold, int32_t ndim, const int32_t* dims,
                          float* ws, double* out, sp_stream_t stream);
 
+/* The same measures for T results against ONE reference -- the time-to-treatment curve of
+ * tester/CaeReconstructionTesterCurve.py:18-42, which measures every point against the same follow-up lesion.
+ * results + t * result_stride (floats, >= prod(dims)) is result t; dims / ndim describe ONE volume, as for sp_surface_distances
+ * (an extent-1 axis the array has makes every mask voxel a border voxel).  t is NOT an array axis: no erosion neighbour and no
+ * transform line crosses from one result to the next.  counts[t][4] (zeroed by the caller) is what sp_confusion_counts
+ * yields for (result t, reference), out[t][6] (fp64, zeroed by the caller) what sp_surface_distances yields for it: the
+ * maximum squared distances exact integers, roots and sums in fp64; an empty mask gives count 0.  The reference's border
+ * and transform are computed once, the T result transforms in the same launches; the number of launches (seeds, one scan
+ * per axis of extent > 1, statistics, finish: at most 8) does not depend on T.
+ * ws: 2 * (T + 1) * prod(dims) floats (sp_binary_measures_many_workspace); (T + 1) * prod(dims) < 2^31, T < 65535. */
+int sp_binary_measures_many_workspace(int32_t T, int64_t nvox, int64_t* floats);      /* host only */
+int sp_binary_measures_many(const float* results, int64_t result_stride, int32_t T, const float* reference, float threshold,
+                            int32_t ndim, const int32_t* dims, float* ws, unsigned long long* counts, double* out,
+                            sp_stream_t stream);
+
 /* ------------------------------------------------------------------ signed-distance-map baseline (csrc/sp_sdm.hip)
  * test_sdm_resampling.py:15-52 of the reference (sdm_interpolate_numpy) on the device, in fp64.  Volumes are C-ordered
  * (D, H, W).  Dtype codes of the zoom's source / output and of the blend's t: */

@@ -77,3 +77,46 @@ class CaeInference(Inference):
         if getattr(self._model, "USES_CTP_INPUTS", False):       # Cae3DCtp: every other model leaves the inputs alone
             dto = self.init_ctp_variables(batch, dto)
         return self.infer(dto)
+
+    def inference_curve(self, batch: dict, steps):
+        """``[inference_step(batch, step) for step in steps]`` (each step a float, or None for the case's own time to treatment) for
+        one case at the cost of one: only the interpolated latent differs between the points of a time-to-treatment curve.  The
+        encoder runs once, the model's own ``_interpolate`` is applied to the stacked normalised times -- every latent is the value
+        the per-step path computes --, and one decoder call reconstructs core, penumbra, lesion and all T interpolations.  Returns
+        one ``CaeDto`` per step; the core / penumbra / lesion tensors are shared between them, the interpolations (latents and
+        reconstructions) are slices of one tensor.  Batch size 1 and an eval-mode model (the testers' setting: in training
+        mode every pass would see batch statistics of its own)."""
+        steps = list(steps)
+        if not steps:
+            return []
+        if batch[data.KEY_GLOBAL].size(0) != 1:
+            raise ValueError("inference_curve evaluates one case at a time (batch size 1), got %d" % batch[data.KEY_GLOBAL].size(0))
+        enc, dec = getattr(self._model, "enc", None), getattr(self._model, "dec", None)
+        if enc is None or dec is None or not hasattr(enc, "_interpolate"):
+            raise TypeError("inference_curve needs an encoder / decoder model (Cae3D, Cae3DCtp), got %s" % type(self._model).__name__)
+        if self._model.training:
+            raise RuntimeError("inference_curve evaluates a model in eval mode: call model.eval() first")
+        first = self.init_clinical_variables(batch, steps[0])
+        g = first.given_variables
+        # the normalised times exactly as the per-step path computes them, stacked: (T, 1, 1, 1, 1)
+        times = torch.cat([self.get_time_to_treatment(batch, g.globals, s) for s in steps], 0).to(g.globals.device)
+        g.time_to_treatment = times[0:1]
+        first.mode = CaeDtoUtil.FLAG_GTRUTH
+        first = self.init_gtruth_segm_variables(batch, first)
+        if getattr(self._model, "USES_CTP_INPUTS", False):
+            first = self.init_ctp_variables(batch, first)
+        first = enc(first)
+        lat = first.latents.gtruth
+        lat_intp = enc._interpolate(lat.core, lat.penu, times)                       # (T, C, d, h, w)
+        rec_all = dec._run_stack(torch.cat([lat.core, lat.penu, lat.lesion, lat_intp], 0))
+        rec_core, rec_penu, rec_lesion, rec_intp = rec_all[0:1], rec_all[1:2], rec_all[2:3], rec_all[3:]
+        dtos = []
+        for k in range(len(steps)):
+            dto = first if k == 0 else CaeDtoUtil.init_dto(g.globals, times[k:k + 1], g.scalar_types.core, g.scalar_types.penu,
+                                                           g.inputs.core, g.inputs.penu, g.gtruth.core, g.gtruth.penu, g.gtruth.lesion)
+            dto.mode = CaeDtoUtil.FLAG_GTRUTH
+            l, r = dto.latents.gtruth, dto.reconstructions.gtruth
+            l.core, l.penu, l.lesion, l.interpolation = lat.core, lat.penu, lat.lesion, lat_intp[k:k + 1]
+            r.core, r.penu, r.lesion, r.interpolation = rec_core, rec_penu, rec_lesion, rec_intp[k:k + 1]
+            dtos.append(dto)
+        return dtos

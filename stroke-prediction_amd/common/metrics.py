@@ -4,7 +4,8 @@
 whole-batch reductions and the backward run as two fused HIP kernels (``sp_dice_sums``, ``sp_dice_bwd``)
 instead of six torch reductions plus temporaries.  The binary measures (metrics.py:31-62: Dice, precision,
 sensitivity, specificity, Hausdorff distance and ASSD as ``medpy.metric.binary`` 0.3.0 defines them) run on the device:
-``sp_confusion_counts`` and ``sp_surface_distances`` (border extraction + exact Euclidean distance transform).  There is
+``sp_confusion_counts`` and ``sp_surface_distances`` (border extraction + exact Euclidean distance transform), or -- T results
+against one target, the points of a time-to-treatment curve -- ``sp_binary_measures_many`` in one enqueue.  There is
 no host implementation here; the checker is ``oracle/measures.py``.
 """
 import numpy
@@ -304,3 +305,68 @@ def binary_measures_torch(result, target, cuda, binary_threshold=0.5, distances=
     result = result.detach().cpu().numpy() if isinstance(result, torch.Tensor) else result
     target = target.detach().cpu().numpy() if isinstance(target, torch.Tensor) else target
     return binary_measures_numpy(result, target, binary_threshold=binary_threshold, distances=distances)
+
+
+_MANY_WS = {}
+
+
+def measures_many_workspace_floats(T, nvox):
+    """floats of workspace ``sp_binary_measures_many`` needs for T results of nvox voxels each: 2 * (T + 1) * nvox"""
+    import ctypes as C
+    from stroke_prediction_amd.runtime import lib as L
+    n = C.c_int64(0)
+    L.call("sp_binary_measures_many_workspace", int(T), int(nvox), C.byref(n))
+    return int(n.value)
+
+
+def binary_measures_many_torch(results, target, cuda, binary_threshold=0.5, distances=None):
+    """``binary_measures_torch(results[t:t+1], target, ...)`` for every leading entry t of ``results`` -- a (T, 1, D, H, W) tensor or
+    a list of (1, 1, D, H, W) tensors -- against ONE ``target`` (1, 1, D, H, W), as a list of ``BinaryMeasuresDto``: the points of
+    the time-to-treatment curve, all measured against the same follow-up lesion.  One enqueue (``sp_binary_measures_many``: the
+    target's border and distance transform once, the T results' in the same launches) and one device -> host read for all T."""
+    distances = DISTANCE_METRICS if distances is None else distances
+    stride = None
+    if not isinstance(results, torch.Tensor):
+        parts = [r.detach() for r in results]
+        step = parts[1].data_ptr() - parts[0].data_ptr() if len(parts) > 1 else 0
+        if len(parts) > 1 and step >= 4 * parts[0].numel() and step % 4 == 0 and all(
+                p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.shape == parts[0].shape and p.shape[0] == 1
+                and p.data_ptr() == parts[0].data_ptr() + k * step for k, p in enumerate(parts)):
+            # equally spaced in memory (slices of one tensor, as inference_curve returns them): measured where they lie
+            results, stride = parts[0].expand((len(parts),) + tuple(parts[0].shape[1:])), step // 4
+        else:
+            results = torch.cat([p.float() for p in parts], 0)
+    if not (results.is_cuda and isinstance(target, torch.Tensor) and target.is_cuda):
+        raise RuntimeError("binary_measures_many_torch (stroke_prediction_amd) measures tensors on the GPU")
+    from stroke_prediction_amd.runtime import lib as L, ops as O
+    r = results if stride is not None else results.detach().float().contiguous()     # (with a stride: only shape and pointer are used)
+    t = target.detach().float().contiguous()
+    T = r.shape[0]
+    if T < 1 or t.shape[0] != 1 or tuple(r.shape[1:]) != tuple(t.shape[1:]):
+        raise ValueError("binary_measures_many_torch: results %s against target %s (want (T, ...) against (1, ...))"
+                         % (tuple(r.shape), tuple(t.shape)))
+    if t.dim() > 5:
+        raise ValueError("surface distances: tensors of rank <= 5 (got %d)" % t.dim())
+    nvox = t.numel()
+    stride = nvox if stride is None else stride
+    dims = torch.tensor(list(t.shape), dtype=torch.int32)            # host array: read by the launcher, not the kernels
+    key = (r.device, T, nvox)
+    if key not in _MANY_WS:
+        _MANY_WS.clear()                                             # one workspace alive at a time
+        _MANY_WS[key] = torch.empty(measures_many_workspace_floats(T, nvox), dtype=torch.float32, device=r.device)
+    # counts[T][4] (uint64) and out[T][6] (fp64) in one 8-byte-element buffer: one read brings both to the host
+    buf = torch.zeros(10 * T, dtype=torch.float64, device=r.device)
+    L.call("sp_binary_measures_many", O.ptr(r), stride, T, O.ptr(t), float(binary_threshold), t.dim(), dims.data_ptr(),
+           O.ptr(_MANY_WS[key]), O.ptr(buf), buf.data_ptr() + 32 * T, O.stream())
+    host = buf.cpu().numpy()
+    counts = host[:4 * T].view(numpy.int64).reshape(T, 4)
+    sd = host[4 * T:].reshape(T, 6)
+    out = []
+    for k in range(T):
+        tp, fp, fn, tn = (float(v) for v in counts[k])
+        m = _measures_from_counts(tp, fp, fn, tn)
+        if distances and tp + fp > 0 and tp + fn > 0:
+            mx_rt, sm_rt, n_r, mx_tr, sm_tr, n_t = (float(v) for v in sd[k])
+            m.hd, m.assd = float(numpy.sqrt(max(mx_rt, mx_tr))), 0.5 * (sm_rt / n_r + sm_tr / n_t)
+        out.append(m)
+    return out

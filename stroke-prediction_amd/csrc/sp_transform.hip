@@ -113,10 +113,8 @@ extern "C" int sp_map_coordinates_linear(const float* image, const float* d0, co
 // O(n) scan per voxel is ~270 fused min-adds per voxel for 4 x 88^3 -- less than a millisecond, no lower-envelope stack.
 struct Dims5 { int n[5]; };
 
-__global__ __launch_bounds__(256) void sd_border_kernel(const float* __restrict__ x, float thr, Dims5 d, int a0, int64_t total,
-                                                        float* __restrict__ border) {   // a0: first axis the array really has
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
+// is voxel idx of the rank-5 view d a border voxel of the mask x > thr?  a0: first axis the array really has
+__device__ __forceinline__ bool sd_is_border(const float* __restrict__ x, float thr, const Dims5& d, int a0, int64_t idx) {
   int c[5];
   int64_t r = idx;
 #pragma unroll
@@ -133,7 +131,13 @@ __global__ __launch_bounds__(256) void sd_border_kernel(const float* __restrict_
     }
     stride *= d.n[a];
   }
-  border[idx] = (m && !interior) ? 1.f : 0.f;
+  return m && !interior;
+}
+__global__ __launch_bounds__(256) void sd_border_kernel(const float* __restrict__ x, float thr, Dims5 d, int a0, int64_t total,
+                                                        float* __restrict__ border) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  border[idx] = sd_is_border(x, thr, d, a0, idx) ? 1.f : 0.f;
 }
 __global__ __launch_bounds__(256) void sd_seed_kernel(const float* __restrict__ border, int64_t total, float* __restrict__ g) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -216,5 +220,129 @@ extern "C" int sp_surface_distances(const float* result, const float* reference,
   }
   hipLaunchKernelGGL(sd_finish_kernel, dim3(1), dim3(64), 0, st, out);
   SP_CHECK_LAUNCH("sp_surface_distances");
+  return SP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ T results, one reference
+// The time-to-treatment curve (tester/CaeReconstructionTesterCurve.py) measures T predictions against ONE follow-up lesion.
+// The T + 1 volumes (results 0 .. T-1, then the reference) are transformed side by side: volume v is a grid dimension of
+// the seed kernel and part of the OUTER index of the axis scan (sp_edt.h), so no erosion neighbour and no scan line
+// leaves its volume, and the reference's border and transform exist once.  A transform is 0 exactly at its own seeds
+// (every other voxel is at squared distance >= 1 from one), so the transformed volume doubles as its border mask: no
+// border arrays.  Launches: seed, one scan per axis of extent > 1, statistics, finish -- whatever T is.
+__global__ __launch_bounds__(256) void bm_seed_kernel(const float* __restrict__ results, int64_t stride, int T,
+                                                      const float* __restrict__ reference, float thr, Dims5 d, int a0, int64_t total,
+                                                      float* __restrict__ g) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int v = blockIdx.y;
+  const float* x = v < T ? results + (int64_t)v * stride : reference;
+  g[(int64_t)v * total + idx] = sd_is_border(x, thr, d, a0, idx) ? 0.f : SP_SD_BIG;
+}
+// grid (blocks, T, 2).  z = 0: transform of the reference sampled at the border of result t -> out[t][0..2], and the
+// confusion counts of the pair -> counts[t][0..3];  z = 1: transform of result t sampled at the reference's border -> out[t][3..5]
+__global__ __launch_bounds__(256) void bm_stats_kernel(const float* __restrict__ g, int T, int64_t total,
+                                                       const float* __restrict__ results, int64_t stride,
+                                                       const float* __restrict__ reference, float thr,
+                                                       unsigned long long* __restrict__ counts, double* __restrict__ out) {
+  const int t = blockIdx.y, dir = blockIdx.z;
+  const float* gown = g + (int64_t)t * total;
+  const float* gref = g + (int64_t)T * total;
+  const float* at = dir == 0 ? gown : gref;
+  const float* gv = dir == 0 ? gref : gown;
+  const float* r = results + (int64_t)t * stride;
+  float mx = 0.f;
+  double sm = 0.0, cnt = 0.0;
+  unsigned int c[4] = {0, 0, 0, 0};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    if (at[i] == 0.f) { const float gi = gv[i]; mx = fmaxf(mx, gi); sm += sqrt((double)gi); cnt += 1.0; }
+    if (dir == 0) {
+      const bool a = r[i] > thr, b = reference[i] > thr;
+      c[0] += a && b; c[1] += a && !b; c[2] += !a && b; c[3] += !a && !b;
+    }
+  }
+  __shared__ float rm[4];
+  __shared__ double rs[2][4];
+  __shared__ unsigned int rc[4][4];
+  float wm = mx;
+  for (int o = 32; o > 0; o >>= 1) wm = fmaxf(wm, __shfl_xor(wm, o));
+  const double ws = wave_sum_d(sm), wc = wave_sum_d(cnt);
+  const int w = threadIdx.x >> 6;
+  if (dir == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      unsigned int v = c[k];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      if ((threadIdx.x & 63) == 0) rc[k][w] = v;
+    }
+  }
+  if ((threadIdx.x & 63) == 0) { rm[w] = wm; rs[0][w] = ws; rs[1][w] = wc; }
+  __syncthreads();
+  double* o3 = out + (int64_t)t * 6 + 3 * dir;
+  if (threadIdx.x == 0) {
+    const float m4 = fmaxf(fmaxf(rm[0], rm[1]), fmaxf(rm[2], rm[3]));
+    // non-negative floats order like their bit patterns: the maximum through an integer atomic on the double's slot
+    atomicMax(reinterpret_cast<unsigned long long*>(&o3[0]), (unsigned long long)__float_as_uint(m4));
+    atomicAdd(&o3[1], rs[0][0] + rs[0][1] + rs[0][2] + rs[0][3]);
+    atomicAdd(&o3[2], rs[1][0] + rs[1][1] + rs[1][2] + rs[1][3]);
+  }
+  if (dir == 0 && threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    atomicAdd(&counts[(int64_t)t * 4 + k], (unsigned long long)rc[k][0] + rc[k][1] + rc[k][2] + rc[k][3]);
+  }
+}
+__global__ __launch_bounds__(256) void bm_finish_kernel(double* out, int T) {      // the maxima were accumulated as float bit patterns
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= T) return;
+  double* o = out + (int64_t)t * 6;
+  o[0] = (double)__uint_as_float((unsigned)*reinterpret_cast<unsigned long long*>(&o[0]));
+  o[3] = (double)__uint_as_float((unsigned)*reinterpret_cast<unsigned long long*>(&o[3]));
+}
+
+extern "C" int sp_binary_measures_many_workspace(int32_t T, int64_t nvox, int64_t* floats) {
+  SP_CHECK_ARG(floats && T >= 1 && nvox >= 1, "sp_binary_measures_many_workspace: bad arguments");
+  *floats = 2 * ((int64_t)T + 1) * nvox;
+  return SP_OK;
+}
+
+extern "C" int sp_binary_measures_many(const float* results, int64_t result_stride, int32_t T, const float* reference, float threshold,
+                                       int32_t ndim, const int32_t* dims, float* ws, unsigned long long* counts, double* out,
+                                       sp_stream_t stream) {
+  SP_CHECK_ARG(results && reference && dims && ws && counts && out && ndim >= 1 && ndim <= 5, "sp_binary_measures_many: bad arguments");
+  SP_CHECK_ARG(T >= 1 && T < 65535, "sp_binary_measures_many: T = %d outside [1, 65535)", T);
+  Dims5 d;
+  int64_t total = 1;
+  for (int a = 0; a < 5; ++a) {
+    const int src = a - (5 - ndim);
+    d.n[a] = src >= 0 ? dims[src] : 1;
+    SP_CHECK_ARG(d.n[a] >= 1, "sp_binary_measures_many: empty axis");
+    total *= d.n[a];
+    SP_CHECK_ARG(total < (1ll << 31), "sp_binary_measures_many: 2^31 voxels or more");
+  }
+  const int64_t all = ((int64_t)T + 1) * total;
+  SP_CHECK_ARG(all < (1ll << 31), "sp_binary_measures_many: (T + 1) * prod(dims) = %lld is 2^31 or more", (long long)all);
+  SP_CHECK_ARG(T == 1 || result_stride >= total, "sp_binary_measures_many: result stride %lld below the volume's %lld elements",
+               (long long)result_stride, (long long)total);
+  const int a0 = 5 - ndim;      // as in sp_surface_distances: only the axes the array has are tested by the erosion
+  hipStream_t st = ST(stream);
+  float* a_ = ws; float* b_ = ws + all;
+  const unsigned vgrid = (unsigned)((total + 255) / 256), agrid = (unsigned)((all + 255) / 256);
+  hipLaunchKernelGGL(bm_seed_kernel, dim3(vgrid, (unsigned)T + 1), dim3(256), 0, st, results, result_stride, T, reference, threshold, d,
+                     a0, total, a_);
+  int64_t inner = 1;
+  for (int a = 4; a >= 0; --a) {
+    if (d.n[a] > 1) {
+      hipLaunchKernelGGL(sd_edt_axis_kernel, dim3(agrid), dim3(256), 0, st, (const float*)a_, b_, all, d.n[a], inner);
+      float* t_ = a_; a_ = b_; b_ = t_;
+    }
+    inner *= d.n[a];
+  }
+  const int64_t want = (total + 256 * 16 - 1) / (256 * 16);
+  const unsigned sg = (unsigned)(want < 1 ? 1 : (want > 64 ? 64 : want));
+  hipLaunchKernelGGL(bm_stats_kernel, dim3(sg, (unsigned)T, 2), dim3(256), 0, st, (const float*)a_, T, total, results, result_stride,
+                     reference, threshold, counts, out);
+  hipLaunchKernelGGL(bm_finish_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, out, T);
+  SP_CHECK_LAUNCH("sp_binary_measures_many");
   return SP_OK;
 }
