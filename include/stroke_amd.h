@@ -131,9 +131,10 @@ typedef struct sp_conv_args {
   float act_param;
   int32_t dma;                 /* 1: LDS-DMA staging (bf16 in, in_scale NULL, lane-linear planes, +1 KiB LDS slack) */
   int32_t zfill;               /* dma only: taps can leave the input volume -> zero those chunks */
-  int32_t persist;             /* dma only: 1/2 allow the persistent double-buffered variant where it applies;
+  int32_t persist;             /* dma only.  sp_conv3d_igemm: 0: tiled kernel;
                                   3: z-marching ring variant -- ktab then holds (in-plane byte offset | dz) per entry and
-                                  ITH_zs the staged plane height (32 output rows + kernel extent - 1) */
+                                  ITH_zs the staged plane height (32 output rows + kernel extent - 1);
+                                  any other value: SP_EINVAL.  5: what the callers of sp_conv3d_zm pass (not read there) */
   const void* aux;             /* stats_mode 1: tensor shaped like y (the layer input x of a data gradient) */
   int32_t stats_mode;          /* 0: stats = (sum y, sum y^2);  1: stats = (sum y, sum y*aux) -- BatchNorm backward sums
                                   fused into the dgrad epilogue (DMA kernel only) */

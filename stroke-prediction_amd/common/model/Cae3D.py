@@ -67,7 +67,6 @@ class _Lease:
 # 3-4 deep -- with per-layer events keeping the running-statistics updates in pass order and per-pass gradient buffers added up
 # on one stream.  2: in eager launches too.  0: one stream.
 CAE_STREAMS = int(os.environ.get("SP_CAE_STREAMS", "1"))
-_DBG = set(os.environ.get("SP_CAE_DBG", "").split(","))
 _LANE_STREAMS = {}
 _REDUCE_STREAMS = {}
 
@@ -127,7 +126,7 @@ class _StackFn(torch.autograd.Function):
             return (None, None, dx) + tuple(None for _ in range(ctx.nparams))
         names, views, inplace = module._grad_targets()
         red = None
-        if ctx.concurrent and inplace and "nored" not in _DBG:
+        if ctx.concurrent and inplace:
             # sibling passes run their backward on other streams at the same time: accumulate into this context's own buffer,
             # then add it to the stack's segment of the flat gradient buffer on ONE stream (adds of all passes in issue order)
             priv, grads = sc.private_grads(names, views)
@@ -148,7 +147,7 @@ class _StackFn(torch.autograd.Function):
             if red is not None:
                 torch.cuda.current_stream().wait_stream(red)      # every pass of this stack has queued its add by now
             module._stack_grads_final()
-        if ctx.concurrent and ctx.home is not None and ctx.home != torch.cuda.current_stream() and "nojoin" not in _DBG:
+        if ctx.concurrent and ctx.home is not None and ctx.home != torch.cuda.current_stream():
             # autograd joins a node's stream with its consumers' and with the streams of AccumulateGrad nodes; a pass that
             # returns no gradient tensor (parameters accumulate in place, the encoder input needs none) would otherwise stay
             # un-joined: the optimiser on the home stream would not wait for it, and a stream capture could not end
@@ -324,7 +323,7 @@ class CaeBase(FlatParamsMixin, nn.Module):
             s = main if (lane == 0 or not conc) else _lane_stream(dev, lane)
             if s is not main:
                 s.wait_event(fork_ev)
-            rec = [torch.cuda.Event() for _ in range(nlayers)] if (conc and training and lane + 1 < n and "noorder" not in _DBG) else None
+            rec = [torch.cuda.Event() for _ in range(nlayers)] if (conc and training and lane + 1 < n) else None
             with torch.cuda.stream(s):
                 outs[i] = self._run_stack(xs[i], dict(lane=lane, sc=scs[lane], concurrent=conc, home=main, bump_nbt=nbt is None,
                                                       order=(prev, rec) if (conc and training) else None, **(one(xs[i]) or {})))
@@ -333,8 +332,7 @@ class CaeBase(FlatParamsMixin, nn.Module):
             for lane, i in enumerate(idx):
                 if lane:
                     main.wait_stream(_lane_stream(dev, lane))
-                    if "norecord" not in _DBG:
-                        outs[i].record_stream(main)
+                    outs[i].record_stream(main)
         return outs
 
     def _run_stack_batched(self, xs, idx, ctp=None):

@@ -500,6 +500,7 @@ extern "C" int sp_conv3d_igemm(const sp_conv_args* a, sp_stream_t stream) {
   const int rc = conv_check_build(a, P);
   if (rc != SP_OK) return rc;
   SP_CHECK_ARG(a->group_batch == 0 || (a->group_batch > 0 && a->B % a->group_batch == 0), "sp_conv3d_igemm: group_batch %d does not divide the batch %d", a->group_batch, a->B);
+  SP_CHECK_ARG(a->persist == 0 || a->persist == 3, "sp_conv3d_igemm: persist %d: 0 (tiled kernel) or 3 (z-marching ring variant) only", a->persist);
   if (a->dma) return sp_conv3d_igemm_dma(a, stream);
   dim3 grid(P.nblk, a->NTtot / a->NT);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

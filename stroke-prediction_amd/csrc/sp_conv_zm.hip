@@ -978,8 +978,7 @@ static int launch_zm2(const sp_conv_args* a, const void* zeros, hipStream_t st) 
   Q.d_tx = make_fastdiv(Q.ntx);
   Q.d_ty = make_fastdiv(Q.nty);
   const uint64_t planes = (uint64_t)Q.ncols * a->Do;
-  static const int slots_env_ = getenv("SP_ZM_SLOTS") ? atoi(getenv("SP_ZM_SLOTS")) : 0;
-  const int slots = slots_env_ > 0 ? slots_env_ : 256;               // resident workgroups: one per CU
+  const int slots = 256;               // resident workgroups: one per CU
   unsigned grid = planes / 4 < (uint64_t)slots ? (unsigned)(planes / 4 > 0 ? planes / 4 : 1) : (unsigned)slots;
   if (a->nslices > 1) {      // teams of nslices workgroups per XCD (see the kernel)
     grid = 8u * (unsigned)a->nslices * (32u / (unsigned)a->nslices);
@@ -1078,25 +1077,21 @@ static int launch_zm(const sp_conv_args* a, const void* zeros, hipStream_t st) {
 }
 
 // (P, NT) -> rows per wave, ring slots, waves per workgroup; SP_EINVAL = no kernel.  runtime/plan.py (ZM_CONFIGS) must agree:
-// tests/test_cabi.py checks it.  SP_ZM_NW=4 forces the one-wave-per-SIMD set everywhere (A/B runs; read on both sides).
+// tests/test_cabi.py checks it.
 // three input planes (48 -> 16): eight waves on 24 x 16 tiles and TWO ring slots (three would not fit beside the 41 KB of weight
 // fragments), the prefetched plane's DMAs at the top of the step.  The four-wave form (16 x 16 tiles, three slots) spent 1.8 us of
 // every 2.9 us step outside the MFMAs -- DMA issue, epilogue and barrier of a wave are not covered by a partner on its SIMD --:
-// 161 -> 143 us at 4 x 92^3.  SP_ZM_31=w4 brings it back (A/B runs; read on both sides).
-static bool zm_31w4() { static const bool v = getenv("SP_ZM_31") && !strcmp(getenv("SP_ZM_31"), "w4"); return v; }
-static bool zm_nw4() { static const bool v = getenv("SP_ZM_NW") && atoi(getenv("SP_ZM_NW")) == 4; return v; }
+// 161 -> 143 us at 4 x 92^3.
 extern "C" int sp_conv3d_zm_config(int32_t P, int32_t NT, int32_t* MT, int32_t* NSLOT, int32_t* NW) {
   int mt = 0, ns = 3, nw = 8;
   // eight waves (two per SIMD): one wave's epilogue / DMA / LDS instructions issue under its partner's MFMAs -- measured 12-25 %
-  // faster than four waves with twice the rows each, except for three input planes, where the smaller per-wave tile makes the
-  // LDS weight reads (3 per 6 MFMAs) the limit and the register budget of two waves per SIMD spills
+  // faster than four waves with twice the rows each
   if (P == 1 && NT == 1) mt = 4;
   else if (P == 1 && NT == 2) mt = 2;
   else if (P == 1 && NT == 3) mt = 2;
   else if (P == 2 && NT == 1) mt = 4;
   else if (P == 2 && NT == 2) mt = 2;
-  else if (P == 3 && NT == 1) { mt = 3; ns = 2; if (zm_31w4() || zm_nw4()) { mt = 4; ns = 3; nw = 4; } }
-  if (zm_nw4() && mt && nw == 8) { mt *= 2; nw = 4; }
+  else if (P == 3 && NT == 1) { mt = 3; ns = 2; }
   if (MT) *MT = mt;
   if (NSLOT) *NSLOT = ns;
   if (NW) *NW = nw;
@@ -1222,20 +1217,8 @@ extern "C" int sp_conv3d_zm(const sp_conv_args* a, const void* zeros, sp_stream_
     return SP_EINVAL;
   }
   SP_CHECK_ARG(sp_conv3d_zm_config(P, a->NT, &mt, &ns, &nw) == SP_OK && mt == a->MT, "sp_conv3d_zm: no kernel for P=%d NT=%d MT=%d", P, a->NT, a->MT);
-  // SP_ZM_VARIANT=<digit per (P,NT) class in the order 11 12 13 21 22 31>: tuning knob (tools/bench_conv.py)
-  static const char* var_ = getenv("SP_ZM_VARIANT");
-  auto v = [&](int k) { return (var_ && (int)strlen(var_) > k) ? var_[k] - '0' : 0; };
-  if (nw == 4) {
-    if (P == 1 && a->NT == 1) return launch_zm<1, 1, 8, 3, false, 4>(a, zeros, st);
-    if (P == 1 && a->NT == 2) return launch_zm<1, 2, 4, 3, true, 4>(a, zeros, st);
-    if (P == 1 && a->NT == 3) return launch_zm<1, 3, 4, 3, true, 4>(a, zeros, st);      // (register weights: 180 + 192 accumulator registers spill)
-    if (P == 2 && a->NT == 1) return launch_zm<2, 1, 8, 3, true, 4>(a, zeros, st);
-    if (P == 2 && a->NT == 2) return launch_zm<2, 2, 4, 3, true, 4>(a, zeros, st);
-    if (P == 3 && a->NT == 1) return v(5) == 1 ? launch_zm<3, 1, 4, 3, false, 4>(a, zeros, st) : launch_zm<3, 1, 4, 3, true, 4>(a, zeros, st);
-    return SP_EINVAL;
-  }
   if (P == 3 && a->NT == 1) return launch_zm<3, 1, 3, 2, true, 8>(a, zeros, st);      // (the only eight-wave instance with two ring slots)
-  if (P == 1 && a->NT == 1) return v(0) == 1 ? launch_zm<1, 1, 4, 3, true, 8>(a, zeros, st) : launch_zm<1, 1, 4, 3, false, 8>(a, zeros, st);
+  if (P == 1 && a->NT == 1) return launch_zm<1, 1, 4, 3, false, 8>(a, zeros, st);
   if (P == 1 && a->NT == 2) return launch_zm<1, 2, 2, 3, true, 8>(a, zeros, st);
   if (P == 1 && a->NT == 3) return launch_zm<1, 3, 2, 3, true, 8>(a, zeros, st);
   if (P == 2 && a->NT == 1) return launch_zm<2, 1, 4, 3, true, 8>(a, zeros, st);

@@ -28,9 +28,8 @@ extern "C" void sp_last_error(char* buf, size_t n) {
 extern "C" int sp_version(void) { return 100; }
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
-// grid cap of the grid-stride elementwise kernels: 4096 measured best (2048: +1 % step time, 8192+: +0.5 %; SP_ELEM_BLOCKS)
-static int max_blocks_() { static int v = getenv("SP_ELEM_BLOCKS") ? atoi(getenv("SP_ELEM_BLOCKS")) : 4096; return v; }
-#define MAX_BLOCKS max_blocks_()
+// grid cap of the grid-stride elementwise kernels: 4096 measured best (2048: +1 % step time, 8192+: +0.5 %)
+#define MAX_BLOCKS 4096
 
 // thread -> (voxel slot, octet) for CP/8 octets; threads beyond vpb*OC idle
 struct OctMap {
@@ -1174,7 +1173,7 @@ static int upcat_impl(const void* low, int32_t CPu, const void* skip, int32_t CP
   if (!hl_lo) hl_lo = no_lo_;
   // cat == NULL: only the fp8 copy (and the statistics) are wanted -- rows kernel only
   SP_CHECK_ARG(low && skip && (cat || q8.p) && CPu % 8 == 0 && CPs % 8 == 0 && CPd == CPu + CPs, "sp_upsample2_crop_cat_fwd: bad channels");
-  SP_CHECK_ARG(cat || (cat_plane && CPu % 16 == 0 && CPs % 16 == 0 && (int64_t)B * D * H * W * 4 < (1ll << 31) && !getenv("SP_UPCAT_BLOCKS")),
+  SP_CHECK_ARG(cat || (cat_plane && CPu % 16 == 0 && CPs % 16 == 0 && (int64_t)B * D * H * W * 4 < (1ll << 31)),
                "sp_upsample2_crop_cat_fwd_q8: without the 16-bit output the plane-major form is required");
   SP_CHECK_VOX((int64_t)B * Ds * Hs * Ws, "sp_upsample2_crop_cat_fwd");
   SP_CHECK_ARG(2 * D <= Ds && 2 * H <= Hs && 2 * W <= Ws, "sp_upsample2_crop_cat_fwd: skip smaller than the upsampled grid");
@@ -1182,13 +1181,12 @@ static int upcat_impl(const void* low, int32_t CPu, const void* skip, int32_t CP
   SP_CHECK_ARG(cat_plane == 0 || CPd % 16 == 0, "sp_upsample2_crop_cat_fwd: plane-major output needs whole 16-channel planes");
   OctMap om = make_octmap(CPd);
   Dims dl{B, D, H, W}, ds{B, Ds, Hs, Ws};
-  if (cat_plane && CPu % 16 == 0 && CPs % 16 == 0 && (int64_t)B * D * H * W * 4 < (1ll << 31) && !getenv("SP_UPCAT_BLOCKS")) {
+  if (cat_plane && CPu % 16 == 0 && CPs % 16 == 0 && (int64_t)B * D * H * W * 4 < (1ll << 31)) {
     const int64_t total = (int64_t)B * D * H * W * 4;     // (output x, channel half) pairs over the source rows
     // workgroups over all planes: 2048 left 2064 workgroups for 1024 resident ones (a third, nearly empty round); swept 2048 .. 65536
-    // at 2 x 168^3 x 96 channels: 752 / 664 / 630 / 643 / 642 us (SP_UPCAT_CAP: the sweep's knob)
-    static const int cap_total_ = getenv("SP_UPCAT_CAP") ? atoi(getenv("SP_UPCAT_CAP")) : 8192;
-    SP_CHECK_ARG(cap_total_ >= 8, "sp_upsample2_crop_cat_fwd: SP_UPCAT_CAP %d", cap_total_);
-    const int64_t want = (total + 1023) / 1024, cap = cap_total_ / (CPd / 16) + 1;
+    // at 2 x 168^3 x 96 channels: 752 / 664 / 630 / 643 / 642 us
+    constexpr int UPCAT_CAP_TOTAL = 8192;
+    const int64_t want = (total + 1023) / 1024, cap = UPCAT_CAP_TOTAL / (CPd / 16) + 1;
     const unsigned gx = ((unsigned)(want < cap ? want : cap) + 7) / 8 * 8;
     dim3 grid(gx * (unsigned)(CPd / 16));
     SP_CHECK_ARG(!q8.p || (dtype == SP_BF16 && q8.plane >= (int64_t)B * D * H * W * 8 * 16 && q8.scale > 0.f), "sp_upsample2_crop_cat_fwd_q8: bf16 tensors only");
@@ -1895,16 +1893,14 @@ static int upsample2_act_bwd_impl(const void* y, const void* cat, const void* g,
   SP_CHECK_VOX((int64_t)B * D * H * W * 8, "sp_upsample2_act_bwd");
   OctMap om = make_octmap(CP);
   Dims di{B, D, H, W};
-  static const bool ring_groups_ = !getenv("SP_UPSAMPLE_BWD_NO_GROUPS");      // (A/B knob: 128 / 256 channels on the tiled kernel)
-  if (dtype == SP_BF16 && (CP == 16 || CP == 32 || CP == 64 || (ring_groups_ && (CP == 128 || CP == 256))) && D >= 2 && H >= 2 && W >= 2 &&
+  if (dtype == SP_BF16 && (CP == 16 || CP == 32 || CP == 64 || CP == 128 || CP == 256) && D >= 2 && H >= 2 && W >= 2 &&
       (int64_t)4 * H * W * CPcat * 2 < (1ll << 31) && !getenv("SP_UPSAMPLE_BWD_TILED") && !getenv("SP_UPSAMPLE_BWD_GATHER")) {
     if (CP == 16) return launch_up_bwd_ring<2>(y, g, coef, CPcat, coef_stride, di, act, act_param, dz, dbias_sums, q8, ST(stream));
     if (CP == 32) return launch_up_bwd_ring<4>(y, g, coef, CPcat, coef_stride, di, act, act_param, dz, dbias_sums, q8, ST(stream));
     // 64 channels as two groups of 32: the 4-row tile of the 32-channel instance has less halo (1.33x against 1.59x), and the
     // two groups of a position run side by side on one XCD (workgroup ids 128 apart), sharing the lines they both touch
     // (64 -> 32 @84^3 + 168^3: 596 -> 559 us; fp8 4-scale step 19.8 -> 19.6 ms)
-    static const bool split64_ = getenv("SP_UPBWD_NO_SPLIT64") == nullptr;
-    if (split64_ && CP == 64) return launch_up_bwd_ring<4>(y, g, coef, CPcat, coef_stride, di, act, act_param, dz, dbias_sums, q8, ST(stream), 2);
+    if (CP == 64) return launch_up_bwd_ring<4>(y, g, coef, CPcat, coef_stride, di, act, act_param, dz, dbias_sums, q8, ST(stream), 2);
     return launch_up_bwd_ring<8>(y, g, coef, CPcat, coef_stride, di, act, act_param, dz, dbias_sums, q8, ST(stream), CP / 64);
   }
   if (256 % om.OC == 0 && D >= 2 && H >= 2 && W >= 2 && !getenv("SP_UPSAMPLE_BWD_GATHER")) {

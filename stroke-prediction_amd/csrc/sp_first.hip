@@ -18,6 +18,7 @@ constexpr int FT_TZ = 2, FT_TY = 4, FT_TX = 64;          // output voxels per ti
 constexpr int FT_XZ = FT_TZ + 2, FT_XY = FT_TY + 2;      // staged input rows
 constexpr int FT_XP = 72;                                 // staged row pitch in voxels (>= TX + 2 + read-ahead)
 constexpr int FT_ROWS = FT_XZ * FT_XY;
+constexpr unsigned FIRST_MAX_BLOCKS = 2048u;               // grid cap of the persistent forward kernels
 
 struct FirstDev {
   const float* x;                                         // [B][2][D][H][W] fp32
@@ -413,8 +414,7 @@ extern "C" int sp_first_conv_fwd_n(const float* x, int32_t B, int32_t D, int32_t
   SP_CHECK_ARG(!y8 || y8_plane >= (int64_t)B * (D - 2) * (H - 2) * (W - 2) * 16, "sp_first_conv_fwd: y8_plane smaller than a plane of the output");
   FirstDev P;
   SP_CHECK_ARG(first_geometry(P, x, B, D, H, W) == 0, "sp_first_conv_fwd: too many tiles");
-  static const unsigned cap_ = getenv("SP_FIRST_BLOCKS") ? (unsigned)atoi(getenv("SP_FIRST_BLOCKS")) : 2048u;
-  const unsigned grid = P.ntiles < cap_ ? P.ntiles : cap_;
+  const unsigned grid = P.ntiles < FIRST_MAX_BLOCKS ? P.ntiles : FIRST_MAX_BLOCKS;
   if (Cout == 16)
     hipLaunchKernelGGL((first_fwd_kernel<1, false>), dim3(grid), dim3(256), 0, ST(stream), P, (const bf16x8*)wfrag, bias_f, act, act_param,
                        (bf16_t*)y, stats, nrep, (unsigned char*)y8, y8_plane, (const bf16x8*)nullptr, (bf16_t*)nullptr);
@@ -432,8 +432,7 @@ extern "C" int sp_first_conv_fwd_hl(const float* x, int32_t B, int32_t D, int32_
   SP_CHECK_ARG(!stats || nrep >= 1, "sp_first_conv_fwd_hl: stats replicas");
   FirstDev P;
   SP_CHECK_ARG(first_geometry(P, x, B, D, H, W) == 0, "sp_first_conv_fwd_hl: too many tiles");
-  static const unsigned cap_ = getenv("SP_FIRST_BLOCKS") ? (unsigned)atoi(getenv("SP_FIRST_BLOCKS")) : 2048u;
-  const unsigned grid = P.ntiles < cap_ ? P.ntiles : cap_;
+  const unsigned grid = P.ntiles < FIRST_MAX_BLOCKS ? P.ntiles : FIRST_MAX_BLOCKS;
   if (Cout == 16)
     hipLaunchKernelGGL((first_fwd_kernel<1, true>), dim3(grid), dim3(256), 0, ST(stream), P, (const bf16x8*)wfrag_hi, bias_f, act, act_param,
                        (bf16_t*)y, stats, nrep, (unsigned char*)nullptr, (int64_t)0, (const bf16x8*)wfrag_lo, (bf16_t*)y_lo);

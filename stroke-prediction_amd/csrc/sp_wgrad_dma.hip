@@ -446,7 +446,7 @@ static int launch_wgrad_zs(const sp_wgrad_args* a, int COB, hipStream_t st) {
   P.ncols = (uint32_t)cols_xy;
   P.d_tx = make_fastdiv(P.ntx); P.d_ty = make_fastdiv(P.nty); P.d_zc = make_fastdiv(P.nzc); P.d_xw = make_fastdiv(P.XW);
   const uint32_t gx = a->nblocks;
-  P.xcd = (gx % 8 == 0 && gx >= 8 && !getenv("SP_WGRAD_NOXCD")) ? 1 : 0;
+  P.xcd = (gx % 8 == 0 && gx >= 8) ? 1 : 0;
   const int lds_bytes = 4 * P.XPB + 2 * COB * 8192;
   dim3 grid(gx, (a->CoT + COB - 1) / COB, a->CiT);
 #define WZ_CASE(C_)                                                                                  \
@@ -527,7 +527,7 @@ int sp_conv3d_wgrad_dma(const sp_wgrad_args* a, sp_stream_t stream) {
   const int lds_bytes = 2 * P.buf_bytes;
   uint32_t gx = (a->parts || a->nblocks < (int64_t)nt) ? a->nblocks : (uint32_t)nt;   // parts: every block is written
   dim3 grid(gx, (a->CoT + COB - 1) / COB, (a->CiT + CIB - 1) / CIB);
-  P.xcd = (gx % 8 == 0 && gx >= 8 && !getenv("SP_WGRAD_NOXCD")) ? 1 : 0;
+  P.xcd = (gx % 8 == 0 && gx >= 8) ? 1 : 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #define WD_CASE(C_, I_)                                                                              \
   if (COB == C_ && CIB == I_) {                                                                      \
@@ -691,8 +691,8 @@ static int wgrad_finish_folded_impl(float* dw_acc, int32_t nparts, const int32_t
   SP_CHECK_ARG(nparts >= 1 && Cout <= (total + 31) / 32 * 256, "sp_wgrad_finish_folded: nparts");      // (dbias_grad: one thread per output channel)
   SP_CHECK_ARG(!bn_sums || (w_for_bn && bn_nrep >= 1), "sp_wgrad_finish_folded: bn_sums needs the weights and a replica count");
   if (bn_cp <= 0) bn_cp = CiP;
-  static const int tile_max_ = getenv("SP_WGRAD_FINISH_TILE") ? atoi(getenv("SP_WGRAD_FINISH_TILE")) : 32;      // (0: off; A/B knob)
-  if (nparts > 1 && nparts <= tile_max_ && ntap == 27 && CiP % 32 == 0 && (int64_t)CoP * (CiP / 32) >= 512) {
+  constexpr int WGRAD_FINISH_TILE_MAX_PARTS = 32;      // most partial blocks the tile kernel is used for (more, smaller blocks: the kernel above)
+  if (nparts > 1 && nparts <= WGRAD_FINISH_TILE_MAX_PARTS && ntap == 27 && CiP % 32 == 0 && (int64_t)CoP * (CiP / 32) >= 512) {
     hipLaunchKernelGGL(wgrad_finish_folded_tile_kernel<27>, dim3((unsigned)(CiP / 32), (unsigned)CoP), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), dw_acc, nparts, tapsrc, CoP, CiP, Cout, Cin, sCo, sCi, scale, shift,
                        dbias_sums, dw, dbias_grad, w_for_bn, bn_sums, bn_nrep, bn_cp, dbias_stride, acc_scale);

@@ -2,7 +2,6 @@
 enqueues hand-written gfx950 kernels through ``libstroke_amd.so`` (no torch compute kernels)."""
 import math
 import os
-import sys
 import ctypes as C
 
 import numpy as np
@@ -34,18 +33,12 @@ def bump_param_epoch():
 
 FUSE_BN_FINALIZE = bool(int(os.environ.get("SP_FUSE_BN_FINALIZE", "1")))   # sp_bn_finalize inside the weight re-pack kernel of the folded layers (one launch less per layer)
 SPLIT_G = bool(int(os.environ.get("SP_SPLIT_G1", "1")))   # one-launch split of a concatenating layer's data gradient into two dense tensors (ConvRunner.zm_split_ok)
-PSER_FALLBACK = bool(int(os.environ.get("SP_ZM_PSER_FALLBACK", "0")))   # plane-serial march for ops with no whole-set instance (bf16 96 -> 32): 124 us against 95 us on the tiled kernel (off)
 HL_PSER_SLICES = bool(int(os.environ.get("SP_HL_PSER_SLICES", "0")))   # pair mode: 96 -> 32 as two plane-serial launches of 16 output channels -- measured: 2 x 134 us against 275 us on the tiled kernel, no gain (off)
 FUSE_POOL = bool(int(os.environ.get("SP_FUSE_POOL", "1")))   # MaxPool3d(2) in the epilogue of the down blocks' second convolution (training steps)
 FUSE_DZ = bool(int(os.environ.get("SP_FUSE_DZ", "1")))   # the second convolution's data gradient writes the first one's dz (BatchNorm / activation backward in its epilogue)
 BN_SUMS_FROM_WGRAD = not os.environ.get("SP_BN_SUMS_DGRAD")   # BatchNorm-backward sums from the weight-gradient accumulator (layers.py)
 MATERIALIZE_BN = not os.environ.get("SP_NO_MATERIALIZE_BN")   # padded convs behind a BatchNorm: write the normalised input once, then DMA kernels (layers.py)
 WGRAD_PARTS = not os.environ.get("SP_WGRAD_ATOMICS")      # weight-gradient partial blocks + summing finish instead of fp32 atomics
-# Row-reuse z-marching kernel for single-tile 3x3x3 layers (conv_igemm_zr_kernel: 2.4 MFMAs per LDS fragment read
-# instead of 1).  Opt-in: it removes the LDS-read bound of the 16 -> 16 layers (forward 178 -> 162 us, data gradient
-# 157 -> 157 us at 126^3) but those layers sit at the HBM ridge (216 FLOP per byte of activations in + out), and the
-# second set of weight fragments costs what the forward gains: 4.00 vs 4.00 ms per step.
-USE_ZR = os.environ.get("SP_CONV_ZR", "0") != "0"
 USE_ZM_SLICES = bool(int(os.environ.get("SP_ZM_SLICES", "1")))      # ops with too many output tiles for one z-marching launch: a launch per 32-channel slice
 ZM_SLICE_MIN_PLANES = int(os.environ.get("SP_ZM_SLICE_MIN_PLANES", "2000"))  # ... when the volume is large enough (one launch per slice: 32->96 @48^3 gains nothing, @166^3 40 %; as teams of one launch: @48^3 147 -> 119 us)
 USE_PW_WGRAD = bool(int(os.environ.get("SP_WGRAD_PW", "1")))      # streaming weight-gradient kernel for pointwise layers
@@ -62,7 +55,6 @@ ZM_GROUPS = bool(int(os.environ.get("SP_ZM_GROUPS", "1")))      # batched passes
 ZM_CAE = bool(int(os.environ.get("SP_ZM_CAE", "1")))      # z-marching kernel (ELU epilogue, padding) for the CAE's materialised 3x3x3 layers
 USE_MULTI = bool(int(os.environ.get("SP_CONV_MULTI", "1")))      # parity classes of an op in one launch where the kernel allows
 USE_FC = bool(int(os.environ.get("SP_CONV_FC", "1")))      # split-K kernel for FC-like layers (deep K, tiny output volume)
-USE_PERSIST = bool(int(os.environ.get("SP_CONV_PERSIST", "0")))     # persistent double-buffered conv variant: measured slower than 3 workgroups/CU (272 vs 238 us on 16->16 @126^3), opt-in
 WGRAD_ZS = int(os.environ.get("SP_WGRAD_ZS", "1"))   # z-marching ring variant of the DMA weight gradient (0 off, 1 where it pays, 2 wherever it applies)
 CAT_PLANAR = bool(int(os.environ.get("SP_CAT_PLANAR", "1")))   # plane-major concat buffers (dense 16-channel planes for the DMA consumers)
 USE_ZS = bool(int(os.environ.get("SP_CONV_ZS", "1")))     # z-marching ring conv variant for the 16->16-channel stride-1 layers (-20 %)
@@ -232,18 +224,14 @@ class ConvRunner:
                 lo = torch.empty(frag_elems, dtype=torch.bfloat16, device=device) if op.dtype in (L.SP_F32, L.SP_HL) else None
                 d = dict(sub=sub, kmap=_dev_i32(sub.kmap, device), ktab=_dev_i32(sub.ktab, device),
                          ktab_zs=None if getattr(sub, "ktab_zs", None) is None else _dev_i32(sub.ktab_zs, device),
-                         hi=hi, lo=lo, nsteps=nsteps, ktab_zr=None)
-                if USE_ZR and getattr(sub, "ktab_zr", None) is not None and op.dtype == L.SP_BF16:
-                    # second set of weight fragments in the row-reuse order (15 steps: dy-major)
-                    d.update(ktab_zr=_dev_i32(sub.ktab_zr, device), kmap_zr=_dev_i32(sub.kmap_zr, device),
-                             hi_zr=torch.empty(15 * op.nttot * 64 * 8, dtype=torch.bfloat16, device=device))
+                         hi=hi, lo=lo, nsteps=nsteps)
                 subs.append(d)
             st["subs"] = subs
             zm = P.zm_plan(op, tile=zm_tile) if (USE_ZM and USE_DMA and zm_batch) else None
             # plane-serial march (round 5): the (P, NT, dtype) triples measured faster there (plan.ZM_PSER_PREFER: the pair mode's 48 -> 16).
             # Ops with more input planes than a whole-set ring holds (bf16 96 -> 32) stay on the tiled kernel: 94 us against 124 us
-            # plane-serial in one call (SP_ZM_PSER_FALLBACK=1 routes them here)
-            if USE_ZM and USE_DMA and zm_batch and ((zm is None and PSER_FALLBACK) or P.ZM_PSER_ALL or (op.cpi // 16, -(-op.cout // 16), op.dtype) in P.ZM_PSER_PREFER):
+            # plane-serial in one call
+            if USE_ZM and USE_DMA and zm_batch and (P.ZM_PSER_ALL or (op.cpi // 16, -(-op.cout // 16), op.dtype) in P.ZM_PSER_PREFER):
                 zp = P.zm_pser_plan(op, tile=zm_tile)
                 if zp is not None:
                     zm = zp
@@ -423,8 +411,6 @@ class ConvRunner:
             L.call("sp_conv_prep_folded_bn", ptr(w), op.w_sco, op.w_sci, op.cout, op.cin, ptr(kmap), nsteps, nttot, ptr(hi), ptr(lo), ntaps,
                    ptr(b), ptr(self.bias), nttot * 16, C.byref(bn), stream())
             self.has_bias = True
-            if not self.uses_zm() and self.fc is None:
-                self._prep_zr(w, fold_scale)
             return
         if fold_scale is not None and fold_shift is not None and len(packs) == 1:
             kmap, nsteps, hi, lo, nttot, _, _ = packs[0]
@@ -433,14 +419,10 @@ class ConvRunner:
                    ptr(hi), ptr(lo), ptr(fold_scale), ntaps, ptr(b), ptr(fold_shift), ptr(self.bias), nttot * 16,
                    stream())
             self.has_bias = True
-            if not self.uses_zm() and self.fc is None:
-                self._prep_zr(w, fold_scale)
             return
         for kmap, nsteps, hi, lo, nttot, c0, cn in packs:      # (a slice: element (co', ci', tap) of it is w[(c0 + co') sCo + ci' sCi + tap])
             L.call("sp_conv_prep_weights", w.data_ptr() + 4 * c0 * op.w_sco, op.w_sco, op.w_sci, cn, op.cin, ptr(kmap), nsteps,
                    nttot, ptr(hi), ptr(lo), ptr(fold_scale), stream())
-        if not self.uses_zm() and self.fc is None:
-            self._prep_zr(w, fold_scale)
         if fold_shift is not None:
             ntaps = w.numel() // (op.cin * op.cout)
             L.call("sp_conv_fold_bias", ptr(w), op.w_sco, op.w_sci, op.cout, op.cin, ntaps, ptr(b), ptr(fold_shift),
@@ -449,13 +431,6 @@ class ConvRunner:
         elif b is not None:
             self.bias[:op.cout].copy_(b.detach())
             self.has_bias = True
-
-    def _prep_zr(self, w, fold_scale):
-        op = self.op
-        for s in self.subs:
-            if s.get("ktab_zr") is not None:
-                L.call("sp_conv_prep_weights", ptr(w), op.w_sco, op.w_sci, op.cout, op.cin, ptr(s["kmap_zr"]), 15, op.nttot,
-                       ptr(s["hi_zr"]), None, ptr(fold_scale), stream())
 
     def run(self, x, y, batch, in_scale=None, in_shift=None, act=L.ACT_NONE, act_param=0.0, stats=None,
             dtype_out=None, use_bias=True, stats_nrep=1, stats_mode=0, aux=None, x_planar=False, group_batch=0, y8=None,
@@ -577,16 +552,13 @@ class ConvRunner:
                       "plane_bytes", "lo_offset", "steps_per_group", "lds_bytes", "zfill"):
                 setattr(a, k, t[k])
             a.dma = int(t["dma"] and in_scale is None and USE_DMA)
-            a.persist = 0 if (a.group_batch or op.dtype == L.SP_HL) else int(USE_PERSIST)      # (BatchNorm groups, bf16 pairs: the tiled kernel only)
+            a.persist = 0
             a.x_plane = 0
             if x_planar:
                 assert (a.dma or op.dtype == L.SP_HL) and t["opp"] == 2, "plane-major input: DMA kernel (or the bf16-pair register-staged one) with 16-channel planes only"
                 a.x_plane = batch * int(np.prod(op.in_dims)) * 16
-                a.persist = 0               # (the persistent variants address channels-last rows)
             if USE_ZS and a.dma and s.get("ktab_zs") is not None and stats_mode == 0 and a.CPo >= 16 and not a.group_batch:
                 a.persist, a.ktab, a.ITH_zs = 3, ptr(s["ktab_zs"]), t["ITH_zs"]     # z-marching ring variant
-                if s.get("ktab_zr") is not None and not x_planar:
-                    a.persist, a.ktab, a.wfrag_hi = 4, ptr(s["ktab_zr"]), ptr(s["hi_zr"])   # ... with row reuse
             if multi is not None:       # the parity classes of one op go out in ONE launch (sp_conv3d_igemm_multi)
                 C.memmove(C.byref(multi, si * C.sizeof(L.ConvArgs)), C.byref(a), C.sizeof(L.ConvArgs))
                 continue
@@ -605,11 +577,15 @@ class ConvRunner:
                     L.call("sp_conv3d_igemm_multi", multi, len(self.subs), st)
 
 
+# most 16-channel tiles per side on the DMA weight-gradient kernels (the row-sliding kernel takes any tile counts -- 192->64 @88^3
+# 2155 -> 706 us against the register-staged kernel)
+WGRAD_DMA_MAX_TILES = 64
+
+
 def wgrad_dma_ok(cpi, cpo, dtype):
-    """the DMA weight-gradient kernels apply (whole 16-channel tiles; the tile-count limits are knobs only)"""
+    """the DMA weight-gradient kernels apply (whole 16-channel tiles)"""
     return bool(USE_DMA and dtype == L.SP_BF16 and cpi % 16 == 0 and cpo % 16 == 0
-                and -(-cpo // 16) <= int(os.environ.get("SP_WGRAD_DMA_MAXCOT", "64"))
-                and -(-cpi // 16) <= int(os.environ.get("SP_WGRAD_DMA_MAXCIT", "64")))
+                and -(-cpo // 16) <= WGRAD_DMA_MAX_TILES and -(-cpi // 16) <= WGRAD_DMA_MAX_TILES)
 
 
 def _run_zm_impl(runner, a, x_planar, batch, with_stats, st, z=None, y=None, stats=None, use_bias=True, wfrag=None):
@@ -712,7 +688,7 @@ class WgradRunner:
         strided = (WGRAD_DMA_STRIDED and s == (2, 2, 2) and k in ((3, 3, 3), (2, 2, 2))
                    and all(i + 2 * q >= (o - 1) * 2 + kk for i, o, q, kk in zip(in_dims, out_dims, p, k)))
         self.dma = bool(USE_DMA and dtype == L.SP_BF16 and (unit or strided) and max(p) <= 2 and cpi % 16 == 0 and cpo % 16 == 0
-                        and self.cot <= int(os.environ.get("SP_WGRAD_DMA_MAXCOT", "64")) and self.cit <= int(os.environ.get("SP_WGRAD_DMA_MAXCIT", "64")))   # (limits are knobs: the row-sliding kernel takes any tile counts -- 192->64 @88^3 2155 -> 706 us against the register-staged kernel)
+                        and self.cot <= WGRAD_DMA_MAX_TILES and self.cit <= WGRAD_DMA_MAX_TILES)
         # pointwise layers (1x1x1, stride 1): streaming kernel of csrc/sp_wgrad_pw.hip, BatchNorm folded into the finish as well
         self.pw = bool(USE_PW_WGRAD and WGRAD_PARTS and dtype == L.SP_BF16 and k == (1, 1, 1) and s == (1, 1, 1) and max(p) == 0
                        and cpi % 8 == 0 and cpo % 8 == 0 and tuple(in_dims) == tuple(out_dims))
@@ -758,9 +734,6 @@ class WgradRunner:
                 nb = max(q, nb // q * q)
             a.nblocks = int(os.environ.get("SP_WGRAD_BLOCKS", nb))
             a.parts, self.nparts = 1, a.nblocks
-            if os.environ.get("SP_WGRAD_DEBUG"):
-                print("wgrad %d->%d @%dx%dx%d batch %d: %d partial blocks of %.2f MB (tile grid %d, groups %d)" % (
-                    self.cin, self.cout, a.Di, a.Hi, a.Wi, batch, a.nblocks, total * 4 / 1e6, yz, getattr(self, "groups", 1)), file=sys.stderr)
             self.acc = torch.empty(self.nparts * total, dtype=torch.float32, device=self.device)
         else:
             a.parts, self.nparts = 0, 1
@@ -852,8 +825,7 @@ def prep_batch(pairs):
     # the cached device table holds raw addresses only: key it on every address it contains, so an entry can only be
     # replayed for runners that own exactly those buffers (ids / addresses recycled after an engine was freed)
     tkey = tuple((w.data_ptr(), 0 if b is None else b.data_ptr(), r.bias.data_ptr(), r.op.w_sco, r.op.w_sci, r.op.cout, r.op.cin, r.op.nttot) +
-                 tuple((k.data_ptr(), n, h.data_ptr(), 0 if lo_ is None else lo_.data_ptr(), nt_, c0_, cn_) for k, n, h, lo_, nt_, c0_, cn_ in r._pack()) +
-                 tuple((0 if sub.get("ktab_zr") is None else sub["hi_zr"].data_ptr()) for sub in r.subs)
+                 tuple((k.data_ptr(), n, h.data_ptr(), 0 if lo_ is None else lo_.data_ptr(), nt_, c0_, cn_) for k, n, h, lo_, nt_, c0_, cn_ in r._pack())
                  for r, w, b, _ in todo)
     tab = _prep_tables.get(tkey)
     if tab is None and torch.cuda.is_current_stream_capturing():
@@ -877,10 +849,6 @@ def prep_batch(pairs):
                 first = False
                 items.append((w.data_ptr() + 4 * c0 * r.op.w_sco, r.op.w_sco, r.op.w_sci, cn, r.op.cin, kmap.data_ptr(), nsteps,
                               nttot, hi.data_ptr(), 0 if lo is None else lo.data_ptr(), 0) + bias_fields)
-            for sub in ([] if r.uses_zm() else r.subs):
-                if sub.get("ktab_zr") is not None:
-                    items.append((w.data_ptr(), r.op.w_sco, r.op.w_sci, r.op.cout, r.op.cin, sub["kmap_zr"].data_ptr(), 15,
-                                  r.op.nttot, sub["hi_zr"].data_ptr(), 0, 0, 0, 0, 0, 0))
         arr = np.array(items, dtype=_PREP_ITEM)
         dev = torch.from_numpy(arr.view(np.uint8).copy()).to(todo[0][1].device)
         maxb = max((int(it[6]) * int(it[7]) * 64 + 255) // 256 for it in items)

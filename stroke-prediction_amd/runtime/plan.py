@@ -301,7 +301,6 @@ def _plan_sub(op: ConvOp, sub: SubConv, force_rows=None):
     # 16-channel tile out, stride 1, resident weights.  Same K order (same weight fragments); its table holds the
     # in-plane offset inside a (32 + ext_y - 1) x ITW plane slot, with the tap's z index in the low two bits.
     sub.ktab_zs = None
-    sub.kmap_zr = sub.ktab_zr = None
     if (dma and op.dtype == 0 and s == (1, 1, 1) and ngroups == 1 and opg == 2 and op.cpi == 16 and zs_steps
             and -(-op.cout // 16) <= 2 and ext[0] <= 3 and mt == 8      # (three output tiles: 359 VGPRs, measured 1.7x slower)
             and sub.out_dims[1] >= 32):
@@ -315,22 +314,6 @@ def _plan_sub(op: ConvOp, sub: SubConv, force_rows=None):
             kz[i] = ((t[1] * itw + t[2]) * vsb + (oc % opp) * 16) | t[0]
         sub.ktab_zs = kz
         sub.tile["ITH_zs"] = 31 * s[1] + ext[1]
-        # row-reuse variant (conv_igemm_zr_kernel): one output tile, 3x3x3.  K steps grouped by dy: for every dy the nine
-        # (dz, dx) taps in ONE fixed order, two octets each -> 18 entries = 4.5 steps, padded to 5; step dy*5 + t.  The
-        # fragment of step type t read at input row r then serves dy = 0, 1, 2 (output rows r, r-1, r-2).
-        if -(-op.cout // 16) == 1 and tuple(ext) == (3, 3, 3) and len(sub.taps) == 27:
-            by_dy = {dy: sorted([t for t in sub.taps if t[1] == dy], key=lambda t: (t[0], t[2])) for dy in range(3)}
-            if all(len(v) == 9 for v in by_dy.values()) and \
-                    all([(t[0], t[2]) for t in by_dy[dy]] == [(t[0], t[2]) for t in by_dy[0]] for dy in range(3)):
-                kmap_zr = np.full(15 * 4, -1, dtype=np.int32)
-                ktab_zr = np.zeros(5 * 4, dtype=np.int32)
-                for dy in range(3):
-                    for i, (t, oc) in enumerate([(t, oc) for t in by_dy[dy] for oc in range(2)]):
-                        kmap_zr[dy * 20 + i] = (t[3] << 16) | oc
-                        if dy == 0:
-                            ktab_zr[i] = ((t[2]) * vsb + oc * 16) | t[0]
-                ktab_zr[18] = ktab_zr[16]; ktab_zr[19] = ktab_zr[17]      # zero-weight half step: any valid address
-                sub.kmap_zr, sub.ktab_zr = kmap_zr, ktab_zr
 
 
 def _finish(op: ConvOp):
@@ -367,25 +350,14 @@ def wgrad_taps(k, transposed_roles=False):
 # ------------------------------------------------------------------------------------------------ z-marching plan
 # Output-stationary z-marching kernel (csrc/sp_conv_zm.hip): (P input planes of 16 channels, NT output tiles of 16) ->
 # (MT rows per wave, ring slots, NW waves per workgroup).  Mirrors sp_conv3d_zm_config (tests/test_cabi.py checks that the
-# two agree).  Default: eight waves (two per SIMD -- one wave's epilogue / DMA / LDS instructions issue under its partner's
-# MFMAs), four for three input planes; SP_ZM_NW=4: four waves with twice the rows each everywhere (read on both sides; A/B runs).
-ZM_CONFIGS_NW4 = {(1, 1): (8, 3, 4), (1, 2): (4, 3, 4), (1, 3): (4, 3, 4), (2, 1): (8, 3, 4), (2, 2): (4, 3, 4), (3, 1): (4, 3, 4)}
-ZM_CONFIGS_DEFAULT = {(1, 1): (4, 3, 8), (1, 2): (2, 3, 8), (1, 3): (2, 3, 8), (2, 1): (4, 3, 8), (2, 2): (2, 3, 8), (3, 1): (3, 2, 8)}
-ZM_CONFIGS = ZM_CONFIGS_NW4 if os.environ.get("SP_ZM_NW") == "4" else ZM_CONFIGS_DEFAULT
-if os.environ.get("SP_ZM_31") == "w4":      # A/B: three input planes on four waves, 16 x 16 tiles, three ring slots (the form up to round 5)
-    ZM_CONFIGS = {**ZM_CONFIGS, (3, 1): (4, 3, 4)}
+# two agree).  Eight waves (two per SIMD -- one wave's epilogue / DMA / LDS instructions issue under its partner's MFMAs),
+# with three input planes too: three rows per wave and two ring slots.
+ZM_CONFIGS = {(1, 1): (4, 3, 8), (1, 2): (2, 3, 8), (1, 3): (2, 3, 8), (2, 1): (4, 3, 8), (2, 2): (2, 3, 8), (3, 1): (3, 2, 8)}
 # bf16-pair instances (dtype 2 = SP_HL, the forward convolutions of the "bf16x3" mode): twice the planes per ring slot and hi + lo
 # weight fragments in LDS -> smaller tiles / two ring slots where Cin x Cout grows.  Mirrors sp_conv3d_zm_config_hl.
 ZM_CONFIGS_HL = {(1, 1): (4, 3, 8), (1, 2): (2, 3, 8), (2, 1): (4, 2, 4), (2, 2): (2, 2, 4), (3, 1): (2, 2, 4)}
 ZM_ITW = 18
 HL_DMA = bool(int(os.environ.get("SP_HL_DMA", "1")))      # bf16-pair layers without a z-marching instance on the LDS-DMA tiled kernel (0: register-staged)
-
-
-# (P, NT) instances that exist but lose against their own slices run as teams of one launch (SP_ZM_SPLIT="1,3;..."): measurement knob
-ZM_SPLIT = {tuple(int(v) for v in it.split(",")) for it in os.environ.get("SP_ZM_SPLIT", "").split(";") if it}
-
-
-ZM_TILE = os.environ.get("SP_ZM_TILE", "auto")      # "16": the classic NW MT rows x 16 voxels everywhere (A/B runs)
 
 
 def zm_tile(ho, wo, nw, mt):
@@ -394,12 +366,6 @@ def zm_tile(ho, wo, nw, mt):
     whatever its fill: 50-voxel rows run as 25 x 10 instead of 16 x 16 tiles, 25 instead of 16 tiles per plane), then the
     least staged halo, then the classic shape.  Limits: tw th <= 16 NW MT voxels, (tw + 2)(th + 2) <= (NW MT + 2) 18 staged."""
     rows = nw * mt
-    if ZM_TILE == "16":
-        return 16, rows
-    if "x" in ZM_TILE:      # "32x16": that shape wherever it fits (A/B runs), else the automatic choice
-        tw, th = (int(v) for v in ZM_TILE.split("x"))
-        if tw * th <= 16 * rows and (tw + 2) * (th + 2) <= (rows + 2) * 18 and tw <= 253 and th <= 253:
-            return tw, th
     best = None
     for tw in range(4, min(wo, 253) + 1):
         for th in range(2, min(ho, 253) + 1):
@@ -437,7 +403,7 @@ def zm_plan(op: ConvOp, tile=None):
     if op.cpi % 16 or op.cpo % 16 or op.cin > op.cpi or op.cpo < NT * 16:
         return None
     configs = ZM_CONFIGS_HL if op.dtype == 2 else ZM_CONFIGS      # (pairs: the table addresses the hi planes; the lo planes follow)
-    if (P_, NT) not in configs or ((P_, NT) in ZM_SPLIT and op.dtype == 0):
+    if (P_, NT) not in configs:
         return None
     MT, nslot, nw = configs[(P_, NT)]
     ith = nw * MT + 2                        # compile-time plane pitch of a ring slot: ITH x 18 voxels

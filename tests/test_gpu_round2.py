@@ -32,13 +32,11 @@ LEAKY = 0.01
 
 @pytest.fixture(autouse=True)
 def production_kernel_choices():
-    """tests/test_gpu_kernels.py flips O.USE_PERSIST for its small volumes at import time: these tests measure what the
-    bench runs"""
-    keep = O.USE_PERSIST, O.ZM_MIN_PLANES
-    O.USE_PERSIST = bool(int(os.environ.get("SP_CONV_PERSIST", "0")))
+    """these tests measure what the bench runs"""
+    keep = O.ZM_MIN_PLANES
     O.ZM_MIN_PLANES = 256          # batch 1 here, batch 4 in the bench: every layer the bench runs on the z-marching kernel does so here
     yield
-    O.USE_PERSIST, O.ZM_MIN_PLANES = keep
+    O.ZM_MIN_PLANES = keep
 
 
 def rel_l2(a, b):

@@ -1,4 +1,4 @@
-"""Time one weight-gradient layer (ci co d [d_h d_w]) under the env knobs SP_WGRAD_CIB / SP_WGRAD_DMA_MAXCIT / SP_WGRAD_BLOCKS."""
+"""Time one weight-gradient layer (ci co d [d_h d_w]) under the env knobs SP_WGRAD_CIB / SP_WGRAD_BLOCKS."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
