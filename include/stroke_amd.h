@@ -869,6 +869,27 @@ int sp_gaussian_filter3d(const float* src, float* dst, float* tmp, int32_t n0, i
 int sp_map_coordinates_linear(const float* image, const float* d0, const float* d1, const float* d2, float s0, float s1, float s2,
                               float cval, float* out, int32_t n0, int32_t n1, int32_t n2, sp_stream_t stream);
 
+/* ------------------------------------------------------------------ batch-level elastic deformation (csrc/sp_augment.hip)
+ * data.py:BatchElasticDeform: the deformation above for a whole collated batch in five launches.  Volumes are stored as the
+ * batch holds them, (Z, Y, X) fp32 with X contiguous; voxel (x, y, z) is element [x, y, z] of the per-sample (n0, n1, n2) array.
+ * sp_rng_uniform_pm1: dst[field][e] for nfields (<= 65535) adjacent fields of per_field (< 2^31) elements, uniform in [-1, 1).
+ * Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (e >> 2, field, call & 0xffffffff, call >> 32), output word
+ * e & 3; u = (word >> 8) * 2^-24, value 2u - 1 (exact in fp32).  seed and call are the 64 bits of an unsigned value. */
+int sp_rng_uniform_pm1(float* dst, int32_t nfields, int64_t per_field, int64_t seed, int64_t call, sp_stream_t stream);
+/* sp_gaussian_filter3d of nfields fields adjacent in memory, three launches in all: passes along x, then y, then z (axis 0, 1, 2
+ * of the per-sample array), the same weights, tap order and fmaf -- bit-equal to sp_gaussian_filter3d on each field; nothing
+ * crosses from one field into the next.  tmp = scratch of the size of src; src, dst, tmp: three different buffers. */
+int sp_gaussian_filter3d_batch(const float* src, float* dst, float* tmp, int32_t nfields, int32_t Z, int32_t Y, int32_t X, float sigma,
+                               float truncate, sp_stream_t stream);
+/* One launch: volume v = b * (C0 + C1) + c is channel c of sample b -- in src0 / dst0 (B, C0, Z, Y, X) for c < C0, else channel
+ * c - C0 of src1 / dst1 (B, C1, Z, Y, X); either group may be empty (C = 0, pointers unused).  fields: (B (C0 + C1), 3, Z, Y, X),
+ * the filtered dx, dy, dz of volume v.  out[z, y, x] = trilinear sample of the source at (x + alpha dy, y + alpha dx,
+ * z + alpha_z dz), 0 when a coordinate leaves [0, n - 1]: sp_map_coordinates_linear(image, dy, dx, dz, alpha, alpha, alpha_z, 0).
+ * flip (device, int32[B], or NULL): a non-zero entry reads that sample's sources mirrored along x.  src != dst. */
+int sp_elastic_warp_batch(const float* src0, float* dst0, int32_t C0, const float* src1, float* dst1, int32_t C1, const float* fields,
+                          const int32_t* flip, int32_t B, int32_t Z, int32_t Y, int32_t X, float alpha, float alpha_z,
+                          sp_stream_t stream);
+
 /* ------------------------------------------------------------------ surface distances of the batch metrics
  * metrics.py:42-44 -> medpy 0.3.0 metric.binary.hd / assd (__surface_distances): border = mask XOR binary_erosion(mask)
  * with the cross structure of the array's rank (out-of-bounds = background), exact Euclidean distance transform of the

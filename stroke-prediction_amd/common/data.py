@@ -10,6 +10,8 @@ patch, pad and the layout permutation are index arithmetic (torch views + one co
 HIP kernels ``sp_gaussian_filter3d`` / ``sp_map_coordinates_linear`` (csrc/sp_transform.hip).  Random decisions come
 from the same host generators as in the reference (``random`` / ``numpy.random.RandomState``), so a seeded pipeline
 reproduces the reference's augmentation; ``ElasticDeform(device_noise=True)`` draws the noise on the device instead.
+``BatchElasticDeform`` is the batch-level form: flip + elastic deformation of a whole collated batch in five launches
+(csrc/sp_augment.hip), handed to the loader factories as ``batch_transform``.
 """
 import datetime
 import random
@@ -213,6 +215,105 @@ class ElasticDeform(object):
         return sample
 
 
+class BatchElasticDeform(object):
+    """``HemisphericFlip`` / ``HemisphericFlipFixedToCaseId`` followed by ``ElasticDeform``, for a whole COLLATED batch: a
+    callable on the batch dict (``labels`` (B, C, Z, Y, X) fp32 on the device, ``images`` optional, everything else passed
+    through) that returns a new dict with new tensors.  Five launches whatever B and C are (csrc/sp_augment.hip): the noise
+    of all 3 * B * channels fields, three filter passes over all of them, one warp of every channel volume (which also
+    reads a flipped sample mirrored).  Channels that are flipped but not deformed (images without ``apply_to_images``) take
+    one ``torch.where`` over the batch.  There is no CPU path.
+
+    ``flip``: ``None``; ``"random"`` -- one ``random.random() > 0.5`` toss per sample in sample order, as ``HemisphericFlip``
+    draws them; or a number ``split_id`` -- samples whose ``case_id`` is above it, as ``HemisphericFlipFixedToCaseId``.
+
+    ``noise="philox"``: ``sp_rng_uniform_pm1`` with (``seed``, call) -- ``seed`` defaults to a clock seed like the reference's,
+    the call counter starts at 0 and advances by one per batch, field ``((b * Ctot) + c) * 3 + d`` (deformed label channels
+    first, then deformed image channels; d = dx, dy, dz): an augmented run is reproducible from ``seed`` alone.
+    ``noise="host"``: one ``numpy.random.RandomState`` per sample, drawn from in the per-sample path's order ((n0, n1, n2)
+    arrays, stored transposed), uploaded in one copy: the batch then equals ``HemisphericFlip -> ElasticDeform -> ToTensor ->
+    stack`` on the same generator states.  ``__call__(batch, random_states=, flips=)`` fixes the states / flags (tests)."""
+
+    def __init__(self, alpha=100, sigma=4, apply_to_images=False, flip=None, noise="philox", seed=None):
+        if not (flip is None or flip == "random" or (isinstance(flip, (int, float)) and not isinstance(flip, bool))):
+            raise ValueError("BatchElasticDeform: flip is None, 'random' or a split case id, got %r" % (flip,))
+        if noise not in ("philox", "host"):
+            raise ValueError("BatchElasticDeform: noise is 'philox' or 'host', got %r" % (noise,))
+        self._alpha, self._sigma, self._apply_to_images, self._flip, self._noise = alpha, sigma, apply_to_images, flip, noise
+        if seed is None:
+            seed = datetime.datetime.now().second + datetime.datetime.now().microsecond
+        self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._calls = 0
+
+    def _flags(self, batch, B):
+        if self._flip is None:
+            return None
+        if self._flip == "random":
+            return [random.random() > 0.5 for _ in range(B)]
+        return [int(c) > self._flip for c in batch[KEY_CASE_ID]]
+
+    def _host_noise(self, B, n_ch, shape_zyx, random_states):
+        Z, Y, X = shape_zyx
+        noise = np.empty((B, n_ch, 3, Z, Y, X), dtype=np.float32)
+        for b in range(B):
+            rs = random_states[b] if random_states is not None else None
+            if rs is None:
+                rs = np.random.RandomState(datetime.datetime.now().second + datetime.datetime.now().microsecond)
+            for c in range(n_ch):
+                for d in range(3):
+                    noise[b, c, d] = (rs.rand(X, Y, Z) * 2 - 1).astype(np.float32).transpose(2, 1, 0)
+        return torch.from_numpy(noise)
+
+    def __call__(self, batch, random_states=None, flips=None):
+        from stroke_prediction_amd.runtime import lib as L, ops as O
+        labels = batch[KEY_LABELS]
+        _require_cuda(labels, "BatchElasticDeform")
+        if labels.dim() != 5:
+            raise ValueError("BatchElasticDeform needs (B, C, Z, Y, X) labels, got %r" % (tuple(labels.shape),))
+        B, C, Z, Y, X = labels.shape
+        if X != Y:
+            raise ValueError("elastic_transform needs (n, n, d) volumes (data.py:336-337), got (x, y, z) = %r" % ((X, Y, Z),))
+        images = batch.get(KEY_IMAGES, [])
+        has_images = _present(images)
+        if has_images:
+            _require_cuda(images, "BatchElasticDeform")
+        warp_images = bool(self._apply_to_images and has_images)
+        if warp_images and tuple(images.shape[0:1] + images.shape[2:]) != (B, Z, Y, X):
+            raise ValueError("BatchElasticDeform: images %r do not match labels %r" % (tuple(images.shape), tuple(labels.shape)))
+        if flips is None:
+            flips = self._flags(batch, B)
+        if flips is not None and len(flips) != B:
+            raise ValueError("BatchElasticDeform: %d flip flags for a batch of %d" % (len(flips), B))
+        dev = labels.device
+        flip_dev = torch.tensor([int(bool(f)) for f in flips], dtype=torch.int32).to(dev) if flips is not None and any(flips) else None
+        src0 = labels.contiguous().float()
+        src1 = images.contiguous().float() if warp_images else None
+        C1 = src1.shape[1] if warp_images else 0
+        n_ch, per_field = C + C1, Z * Y * X
+        if self._noise == "philox":
+            noise = torch.empty((B, n_ch, 3, Z, Y, X), dtype=torch.float32, device=dev)
+            call = self._calls & 0xFFFFFFFFFFFFFFFF
+            self._calls += 1
+            as_i64 = lambda u: u - (1 << 64) if u >= (1 << 63) else u
+            L.call("sp_rng_uniform_pm1", O.ptr(noise), B * n_ch * 3, per_field, as_i64(self._seed), as_i64(call), O.stream())
+        else:
+            noise = self._host_noise(B, n_ch, (Z, Y, X), random_states).to(dev)
+        fields, tmp = torch.empty_like(noise), torch.empty_like(noise)
+        L.call("sp_gaussian_filter3d_batch", O.ptr(noise), O.ptr(fields), O.ptr(tmp), B * n_ch * 3, Z, Y, X, float(self._sigma), 4.0,
+               O.stream())
+        dst0 = torch.empty_like(src0)
+        dst1 = torch.empty_like(src1) if warp_images else None
+        L.call("sp_elastic_warp_batch", O.ptr(src0), O.ptr(dst0), C, O.ptr(src1) if warp_images else None,
+               O.ptr(dst1) if warp_images else None, C1, O.ptr(fields), O.ptr(flip_dev) if flip_dev is not None else None, B, Z, Y, X,
+               float(self._alpha), float(self._alpha) * 0.22, O.stream())
+        out = dict(batch)
+        out[KEY_LABELS] = dst0
+        if warp_images:
+            out[KEY_IMAGES] = dst1
+        elif has_images and flip_dev is not None:
+            out[KEY_IMAGES] = torch.where(flip_dev.bool().view(B, 1, 1, 1, 1), torch.flip(images, (-1,)), images)
+        return out
+
+
 class ResamplePlaneXY(object):
     """Down- or upsample every (x, y) slice (data.py:354-381): nearest neighbour (``ndi.zoom(order=0)``) or, with
     ``mode='bilinear'``, first order.  ``scipy.ndimage.zoom`` maps output index ``o`` to input coordinate
@@ -409,13 +510,25 @@ def set_np_seed(workerid):
     np.random.seed(torch.initial_seed() % np.iinfo(np.int32).max)
 
 
-def _loader(dataset, items, batch_size, num_workers, pin_memory, seeded):
+class _CollateThenTransform(object):
+    """``collate_fn`` of a loader with a ``batch_transform``: the default collate, then the transform on the collated batch"""
+
+    def __init__(self, batch_transform):
+        self.batch_transform = batch_transform
+
+    def __call__(self, samples):
+        from torch.utils.data import default_collate
+        return self.batch_transform(default_collate(samples))
+
+
+def _loader(dataset, items, batch_size, num_workers, pin_memory, seeded, batch_transform=None):
     from torch.utils.data import DataLoader
     from torch.utils.data.sampler import SubsetRandomSampler
     if getattr(getattr(dataset, "transform", None), "device", None) is not None:
         num_workers = 0      # the transform chain uploads and runs HIP kernels: a forked worker cannot re-initialise the GPU
+    extra = dict(collate_fn=_CollateThenTransform(batch_transform)) if batch_transform is not None else {}
     return DataLoader(dataset, batch_size=batch_size, sampler=SubsetRandomSampler(items), num_workers=num_workers,
-                      pin_memory=pin_memory, worker_init_fn=set_np_seed if seeded else None)
+                      pin_memory=pin_memory, worker_init_fn=set_np_seed if seeded else None, **extra)
 
 
 def _fold_items(dataset, indices, shuffle, random_seed):
@@ -426,35 +539,37 @@ def _fold_items(dataset, indices, shuffle, random_seed):
 
 
 def split_data_loader3D(modalities, labels, indices, batch_size, random_seed=None, valid_size=0.5, shuffle=True,
-                        num_workers=4, pin_memory=False, train_transform=[], valid_transform=[]):
+                        num_workers=4, pin_memory=False, train_transform=[], valid_transform=[], batch_transform=None):
     """data.py:113-147: one fold -> (training loader, validation loader); the first ``valid_size`` share of the
-    (seed-shuffled) fold validates."""
+    (seed-shuffled) fold validates.  ``batch_transform`` (e.g. ``BatchElasticDeform``): applied to every collated TRAINING
+    batch; the validation loader never gets it."""
     assert 0 <= valid_size <= 1, "[!] valid_size should be in the range [0, 1]."
     assert train_transform and valid_transform, "You must provide at least a numpy-to-torch transformation."
     dev = _pipeline_device()
     ds_train, ds_valid = _dataset(modalities, labels, train_transform, dev), _dataset(modalities, labels, valid_transform, dev)
     items = _fold_items(ds_train, indices, shuffle, random_seed)
     split = int(np.floor(valid_size * len(items)))
-    return (_loader(ds_train, items[split:], batch_size, num_workers, pin_memory, True),
+    return (_loader(ds_train, items[split:], batch_size, num_workers, pin_memory, True, batch_transform),
             _loader(ds_valid, items[:split], batch_size, num_workers, pin_memory, False))
 
 
 def single_data_loader3D(modalities, labels, indices, batch_size, random_seed=None, valid_size=0.5, shuffle=True,
-                         num_workers=4, pin_memory=False, train_transform=[]):
-    """data.py:150-172."""
+                         num_workers=4, pin_memory=False, train_transform=[], batch_transform=None):
+    """data.py:150-172; ``batch_transform``: as for ``split_data_loader3D``."""
     assert train_transform, "You must provide at least a numpy-to-torch transformation."
     ds = _dataset(modalities, labels, train_transform, _pipeline_device())
-    return _loader(ds, _fold_items(ds, indices, shuffle, random_seed), batch_size, num_workers, pin_memory, True)
+    return _loader(ds, _fold_items(ds, indices, shuffle, random_seed), batch_size, num_workers, pin_memory, True, batch_transform)
 
 
 def get_stroke_shape_training_data(modalities, labels, train_transform, valid_transform, fold_indices, ratio, seed=4,
-                                   batchsize=2, split=True):
+                                   batchsize=2, split=True, batch_transform=None):
     """data.py:175-182 (``num_workers=0``: the transforms run in the training process -- here on its GPU)."""
     if split:
         return split_data_loader3D(modalities, labels, fold_indices, batchsize, random_seed=seed, valid_size=ratio,
-                                   train_transform=train_transform, valid_transform=valid_transform, num_workers=0)
+                                   train_transform=train_transform, valid_transform=valid_transform, num_workers=0,
+                                   batch_transform=batch_transform)
     return single_data_loader3D(modalities, labels, fold_indices, batchsize, random_seed=seed, valid_size=ratio,
-                                train_transform=train_transform, num_workers=0), None
+                                train_transform=train_transform, num_workers=0, batch_transform=batch_transform), None
 
 
 get_stroke_prediction_training_data = get_stroke_shape_training_data      # data.py:185-192: the same factory

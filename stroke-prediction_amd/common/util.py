@@ -26,6 +26,8 @@ _EXPERIMENT = [
     ("--dtype", dict(type=str, default="bf16", choices=["bf16", "f32"], help="(MI355X build) storage / MFMA precision of the HIP path")),
     ("--graph", dict(action="store_true", default=False, help="(MI355X build) replay each training step as one hipGraph")),
     ("--fusedadam", dict(action="store_true", default=False, help="(MI355X build) FusedAdam on the flat buffers instead of torch.optim.Adam")),
+    ("--batchaugment", dict(action="store_true", default=False,
+                            help="(MI355X build) CAE training: flip + elastic deformation once per collated batch (data.BatchElasticDeform)")),
 ]
 _CAE = [
     ("--epochs", dict(type=int, default=300, help="Number of epochs")),

@@ -10,13 +10,9 @@
 
 #include "sp_common.h"
 #include "sp_edt.h"
+#include "sp_gauss.h"
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
-#define SP_GAUSS_MAX_RADIUS 64
-
-struct GaussW {
-  float w[2 * SP_GAUSS_MAX_RADIUS + 1];
-};
 
 // one separable pass along `axis`: out[i] = sum_k w[k] * in[i + k - r], zero outside the volume (mode="constant", cval=0)
 __global__ __launch_bounds__(256) void gauss1d_kernel(const float* __restrict__ src, float* __restrict__ dst, int n0, int n1,
@@ -43,12 +39,10 @@ extern "C" int sp_gaussian_filter3d(const float* src, float* dst, float* tmp, in
                                     float truncate, sp_stream_t stream) {
   SP_CHECK_ARG(src && dst && tmp && tmp != src && tmp != dst && src != dst && n0 >= 1 && n1 >= 1 && n2 >= 1 && sigma > 0.f && truncate > 0.f,
                "sp_gaussian_filter3d: bad arguments");
-  const int radius = (int)(truncate * sigma + 0.5f);
+  const int radius = sp_gauss_radius(sigma, truncate);
   SP_CHECK_ARG(radius <= SP_GAUSS_MAX_RADIUS, "sp_gaussian_filter3d: radius %d above %d", radius, SP_GAUSS_MAX_RADIUS);
   GaussW gw;
-  double sum = 0.0, wd[2 * SP_GAUSS_MAX_RADIUS + 1];
-  for (int t = -radius; t <= radius; ++t) { wd[t + radius] = exp(-0.5 * (double)t * t / ((double)sigma * sigma)); sum += wd[t + radius]; }
-  for (int t = 0; t <= 2 * radius; ++t) gw.w[t] = (float)(wd[t] / sum);
+  sp_gauss_weights(sigma, radius, &gw);
   const int64_t total = (int64_t)n0 * n1 * n2;
   SP_CHECK_ARG(total < (1ll << 31), "sp_gaussian_filter3d: 2^31 elements or more");
   const unsigned grid = (unsigned)((total + 255) / 256);

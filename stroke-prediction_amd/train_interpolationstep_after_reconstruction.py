@@ -40,10 +40,13 @@ def train(args):
     optimizer = torch.optim.Adam(params, lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999))
     scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, args.lrsteps) if args.lrsteps else None
     common = [data.ResamplePlaneXY(args.xyresample)]
-    train_tf = common + [data.HemisphericFlip(), data.ElasticDeform(), data.ToTensor()]
+    # --batchaugment: flip + elastic deformation once per collated batch instead of once per sample and channel
+    augment = [] if args.batchaugment else [data.HemisphericFlip(), data.ElasticDeform()]
+    train_tf = common + augment + [data.ToTensor()]
     valid_tf = common + [data.ToTensor()]
     ds_train, ds_valid = data.get_stroke_shape_training_data(IMAGE_VOLUMES, LABEL_VOLUMES, train_tf, valid_tf, args.fold,
-                                                             args.validsetsize, batchsize=args.batchsize)
+                                                             args.validsetsize, batchsize=args.batchsize,
+                                                             batch_transform=data.BatchElasticDeform(flip="random") if args.batchaugment else None)
     print('Size training set:', len(ds_train.sampler.indices), 'samples | Size validation set:', len(ds_valid.sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
     learner = CaeStepLearner(ds_train, ds_valid, cae, optimizer, scheduler, n_epochs=args.epochs,

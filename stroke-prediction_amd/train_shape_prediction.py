@@ -56,10 +56,13 @@ def build_optimizer(args, cae, enc):
 
 def build_loaders(args):
     common = [data.ResamplePlaneXY(args.xyresample), data.HemisphericFlipFixedToCaseId(split_id=args.hemisflipid)]
-    train_tf = common + [data.ElasticDeform(apply_to_images=True), data.ToTensor()]
+    # --batchaugment: the elastic deformation once per collated batch (the case-id flip stays in the chain both loaders share)
+    augment = [] if args.batchaugment else [data.ElasticDeform(apply_to_images=True)]
+    train_tf = common + augment + [data.ToTensor()]
     valid_tf = common + [data.ToTensor()]
     loaders = data.get_stroke_prediction_training_data(MODALITIES, LABEL_VOLUMES, train_tf, valid_tf, args.fold, args.validsetsize,
-                                                       batchsize=args.batchsize)
+                                                       batchsize=args.batchsize,
+                                                       batch_transform=data.BatchElasticDeform(apply_to_images=True) if args.batchaugment else None)
     print('Size training set:', len(loaders[0].sampler.indices), 'samples | Size validation set:', len(loaders[1].sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
     return loaders

@@ -50,11 +50,14 @@ def build_optimizer(args, cae):
 def build_loaders(args):
     resample = [data.ResamplePlaneXY(args.xyresample)]
     # ElasticDeform warps (n, n, d) label volumes on the device; the validation chain only changes the layout
-    train_tf = resample + [data.HemisphericFlip(), data.ElasticDeform(), data.ToTensor()]
+    # (--batchaugment: the same two steps once per collated batch instead of once per sample and channel)
+    augment = [] if args.batchaugment else [data.HemisphericFlip(), data.ElasticDeform()]
+    train_tf = resample + augment + [data.ToTensor()]
     valid_tf = resample + [data.ToTensor()]
     use_validation = not args.steplearning
     loaders = data.get_stroke_shape_training_data(IMAGE_VOLUMES, LABEL_VOLUMES, train_tf, valid_tf, args.fold, args.validsetsize,
-                                                  seed=args.seed, batchsize=args.batchsize, split=use_validation)
+                                                  seed=args.seed, batchsize=args.batchsize, split=use_validation,
+                                                  batch_transform=data.BatchElasticDeform(flip="random") if args.batchaugment else None)
     n_valid = len(loaders[1].sampler.indices) if loaders[1] is not None else 0
     print('Size training set:', len(loaders[0].sampler.indices), 'samples | Size validation set:', n_valid,
           'samples | Capacity batch:', args.batchsize, 'samples')

@@ -56,10 +56,13 @@ def build_loaders(args):
     pad = args.padding
     common = [data.ResamplePlaneXY(args.xyresample), data.HemisphericFlipFixedToCaseId(split_id=args.hemisflipid),
               data.PadImages(pad[0], pad[1], pad[2], pad_value=0)]
-    train_tf = common + [data.ElasticDeform(), data.ToTensor()]
+    # --batchaugment: the elastic deformation once per collated batch (the case-id flip stays in the chain both loaders share)
+    augment = [] if args.batchaugment else [data.ElasticDeform()]
+    train_tf = common + augment + [data.ToTensor()]
     valid_tf = common + [data.ToTensor()]
     loaders = data.get_stroke_shape_training_data(IMAGE_VOLUMES, LABEL_VOLUMES, train_tf, valid_tf, args.fold, args.validsetsize,
-                                                  seed=args.seed, batchsize=args.batchsize)
+                                                  seed=args.seed, batchsize=args.batchsize,
+                                                  batch_transform=data.BatchElasticDeform() if args.batchaugment else None)
     print('Size training set:', len(loaders[0].sampler.indices), 'samples | Size validation set:', len(loaders[1].sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
     return loaders
