@@ -890,6 +890,22 @@ int sp_elastic_warp_batch(const float* src0, float* dst0, int32_t C0, const floa
                           const int32_t* flip, int32_t B, int32_t Z, int32_t Y, int32_t X, float alpha, float alpha_z,
                           sp_stream_t stream);
 
+/* ------------------------------------------------------------------ batched patch gather from the device-resident case cache
+ * (common/data.py: DeviceCaseCache / CachedBatchLoader; csrc/sp_gather.hip).  One launch.  src0 (N, C0, Z, Y, X) /
+ * src1 (N, C1, Z, Y, X): the cached cases, fp32, X contiguous (the ToTensor layout); either group may be empty (C = 0, its
+ * pointers unused).  dst0 (B, C0, d0, h0, w0), dst1 (B, C1, d1, h1, w1) with ext_t = {w_t, h_t, d_t} and pad_t = {px_t, py_t, pz_t}
+ * (host arrays of three).  table (device, int32[B][5]): case, ox, oy, oz, flip per sample; the origin is in padded coordinates.
+ * For dst_t[b, c, z, y, x]: u = ox + x - px_t, v = oy + y - py_t, s = oz + z - pz_t; outside [0, X) x [0, Y) x [0, Z) (or a case
+ * outside [0, N)) -> padval_t; else src_t[case, c, s, v, flip ? X - 1 - u : u].  That is HemisphericFlip -> PadImages(pad_0,
+ * padval_0) -> RandomPatch(w_0, h_0, d_0, pad) -> ToTensor -> stack with group 0 = images and group 1 = labels (pad_1 = 0,
+ * ext_1 = ext_0 - 2 pad: the centre of the image patch); pad 0 and ext = (X, Y, Z) gathers whole volumes.  No origin reads
+ * outside the cache; offsets into it are 64-bit.  Rows are written with 16-byte stores when w_t is a multiple of 4 and dst_t is
+ * 16-byte aligned, one element per lane otherwise.  SP_EINVAL: non-positive extents, B < 1, N < 1, both groups empty, 2^31 or
+ * more voxels per volume, or more than 2^31 - 1 workgroups (256 work items each) for the batch. */
+int sp_patch_gather_batch(const float* src0, float* dst0, int32_t C0, const int32_t* ext0, const int32_t* pad0, float padval0,
+                          const float* src1, float* dst1, int32_t C1, const int32_t* ext1, const int32_t* pad1, float padval1,
+                          const int32_t* table, int32_t N, int32_t B, int32_t Z, int32_t Y, int32_t X, sp_stream_t stream);
+
 /* ------------------------------------------------------------------ surface distances of the batch metrics
  * metrics.py:42-44 -> medpy 0.3.0 metric.binary.hd / assd (__surface_distances): border = mask XOR binary_erosion(mask)
  * with the cross structure of the array's rank (out-of-bounds = background), exact Euclidean distance transform of the

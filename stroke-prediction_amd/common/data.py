@@ -11,7 +11,9 @@ HIP kernels ``sp_gaussian_filter3d`` / ``sp_map_coordinates_linear`` (csrc/sp_tr
 from the same host generators as in the reference (``random`` / ``numpy.random.RandomState``), so a seeded pipeline
 reproduces the reference's augmentation; ``ElasticDeform(device_noise=True)`` draws the noise on the device instead.
 ``BatchElasticDeform`` is the batch-level form: flip + elastic deformation of a whole collated batch in five launches
-(csrc/sp_augment.hip), handed to the loader factories as ``batch_transform``.
+(csrc/sp_augment.hip), handed to the loader factories as ``batch_transform``.  ``device_cache=True`` on the factories keeps
+every case on the device (``DeviceCaseCache``) and builds each batch -- flip, padding, patch, layout, stack -- with one launch of
+``sp_patch_gather_batch`` (csrc/sp_gather.hip; ``CachedBatchLoader``).
 """
 import datetime
 import random
@@ -538,38 +540,236 @@ def _fold_items(dataset, indices, shuffle, random_seed):
     return items
 
 
+# ---------------------------------------------------------------------------------------------- device-resident case cache
+# The loaders above prepare every sample of every batch from scratch: decode (or synthesise) the case, upload it, resample, flip,
+# pad, cut, stack.  ``device_cache=True`` on the factories uploads every case ONCE (``DeviceCaseCache``) and builds a batch with one
+# launch of ``sp_patch_gather_batch`` (csrc/sp_gather.hip) from a small table of (case, origin, flip) rows (``CachedBatchLoader``).
+
+class DeviceCaseCache(object):
+    """Every case of ``dataset`` (or its ``items``) on ``device``, read once.  ``dataset`` carries the deterministic prefix of the
+    transform chain only (``ResamplePlaneXY``, uploading through ``Compose(device=...)`` as the loaders do), so the cached values are
+    those ``to_device`` -> ``ResamplePlaneXY`` -> ``ToTensor`` give: ``images`` (N, C0, Z, Y, X) and ``labels`` (N, C1, Z, Y, X) fp32
+    with X contiguous, ``clinical`` (N, G, 1, 1, 1); an absent group is ``None``.  ``case_ids`` / ``clinical_idx``: per slot;
+    ``slot_of[item]``: the slot of a data set item.  All cases must have the same extents."""
+
+    def __init__(self, dataset, device="cuda", items=None):
+        self.dataset, self.device = dataset, device
+        self.items = list(range(len(dataset))) if items is None else sorted(set(int(i) for i in items))
+        if not self.items:
+            raise ValueError("DeviceCaseCache: no cases to cache")
+        self.slot_of = {item: n for n, item in enumerate(self.items)}
+        self.case_ids, self.clinical_idx = [], []
+        self.images = self.labels = self.clinical = None
+        stores = {KEY_IMAGES: None, KEY_LABELS: None, KEY_GLOBAL: None}
+        for n, item in enumerate(self.items):
+            sample = to_device(dataset[item], device) if device is not None else dataset[item]
+            self.case_ids.append(int(sample[KEY_CASE_ID]))
+            self.clinical_idx.append(sample.get(KEY_CLINICAL_IDX, 0))
+            for k in stores:
+                v = sample.get(k, [])
+                if not _present(v):
+                    if stores[k] is not None:
+                        raise ValueError("DeviceCaseCache: case %d has no %s, earlier cases have" % (self.case_ids[-1], k))
+                    continue
+                v = (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))).float().permute(3, 2, 1, 0)
+                if stores[k] is None:
+                    if n:
+                        raise ValueError("DeviceCaseCache: case %d has %s, earlier cases have none" % (self.case_ids[-1], k))
+                    stores[k] = torch.empty((len(self.items),) + tuple(v.shape), dtype=torch.float32, device=v.device)
+                if tuple(v.shape) != tuple(stores[k].shape[1:]):
+                    raise ValueError("DeviceCaseCache: %s of case %d are (c, z, y, x) = %r, those of case %d %r: all cases must have the "
+                                     "same extents" % (k, self.case_ids[-1], tuple(v.shape), self.case_ids[0], tuple(stores[k].shape[1:])))
+                stores[k][n].copy_(v)
+        self.images, self.labels, self.clinical = stores[KEY_IMAGES], stores[KEY_LABELS], stores[KEY_GLOBAL]
+        if self.images is None and self.labels is None:
+            raise ValueError("DeviceCaseCache: the data set yields neither images nor labels")
+        if self.images is not None and self.labels is not None and self.images.shape[2:] != self.labels.shape[2:]:
+            raise ValueError("DeviceCaseCache: images %r and labels %r differ in extents" % (tuple(self.images.shape), tuple(self.labels.shape)))
+        self.shape_zyx = tuple((self.images if self.images is not None else self.labels).shape[2:])
+
+    def __len__(self):
+        return len(self.items)
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.images, self.labels, self.clinical) if t is not None)
+
+
+def _gather_launch(cache, table, ext0, pad0, padval0, ext1, pad1):
+    """The one ``sp_patch_gather_batch`` launch of a batch: ``table`` (host int32 (B, 5): slot, ox, oy, oz, flip) goes up in one small
+    pinned copy; returns (images (B, C0, d0, h0, w0) or ``[]``, labels (B, C1, d1, h1, w1) or ``[]``, the device table)."""
+    import ctypes
+    from stroke_prediction_amd.runtime import lib as L, ops as O
+    src0, src1 = cache.images, cache.labels
+    _require_cuda(src0 if src0 is not None else src1, "CachedBatchLoader")
+    dev = (src0 if src0 is not None else src1).device
+    B = int(table.shape[0])
+    Z, Y, X = cache.shape_zyx
+    table_dev = table.pin_memory().to(dev, non_blocking=True)
+    dst0 = torch.empty((B, src0.shape[1], ext0[2], ext0[1], ext0[0]), dtype=torch.float32, device=dev) if src0 is not None else None
+    dst1 = torch.empty((B, src1.shape[1], ext1[2], ext1[1], ext1[0]), dtype=torch.float32, device=dev) if src1 is not None else None
+    i3 = lambda v: (ctypes.c_int32 * 3)(*[int(a) for a in v])
+    L.call("sp_patch_gather_batch", O.ptr(src0), O.ptr(dst0), src0.shape[1] if src0 is not None else 0, i3(ext0), i3(pad0), float(padval0),
+           O.ptr(src1), O.ptr(dst1), src1.shape[1] if src1 is not None else 0, i3(ext1), i3(pad1), 0.0, O.ptr(table_dev), len(cache), B,
+           Z, Y, X, O.stream())
+    return (dst0 if dst0 is not None else []), (dst1 if dst1 is not None else []), table_dev
+
+
+_CHAIN_ORDER = ("ResamplePlaneXY", "flip", "PadImages", "RandomPatch", "ToTensor")
+
+
+def _parse_chain(transforms):
+    """A script's transform list -> {stage: transform}: [ResamplePlaneXY] [HemisphericFlipFixedToCaseId | HemisphericFlip] [PadImages]
+    [RandomPatch] ToTensor, in this order.  Anything else -- the per-sample ``ElasticDeform`` included -- is a ``ValueError``."""
+    stages, last = {}, -1
+    for t in transforms:
+        if isinstance(t, ResamplePlaneXY):
+            stage = 0
+        elif isinstance(t, (HemisphericFlipFixedToCaseId, HemisphericFlip)):
+            stage = 1
+        elif isinstance(t, PadImages):
+            stage = 2
+        elif isinstance(t, RandomPatch):
+            stage = 3
+        elif isinstance(t, ToTensor):
+            stage = 4
+        else:
+            raise ValueError("CachedBatchLoader: %s cannot run from the device cache (the gather does ResamplePlaneXY, HemisphericFlip"
+                             "[FixedToCaseId], PadImages, RandomPatch, ToTensor); hand a batch-level transform such as BatchElasticDeform to "
+                             "batch_transform= instead" % type(t).__name__)
+        if stage <= last:
+            raise ValueError("CachedBatchLoader: %s out of order; the chain is [ResamplePlaneXY] [HemisphericFlipFixedToCaseId | "
+                             "HemisphericFlip] [PadImages] [RandomPatch] ToTensor" % type(t).__name__)
+        stages[_CHAIN_ORDER[stage]] = t
+        last = stage
+    if last != 4:
+        raise ValueError("CachedBatchLoader: the chain must end in ToTensor")
+    return stages
+
+
+class CachedBatchLoader(object):
+    """The loader of ``_loader`` over a ``DeviceCaseCache``: the same index order (``SubsetRandomSampler`` + ``BatchSampler``,
+    ``drop_last=False``), the same batch dict (keys, dtypes, shapes, devices) as the collated batch of the per-sample chain
+    ``transforms``, built per batch by one pinned upload of the (B, 5) table, one ``sp_patch_gather_batch`` launch and one
+    ``index_select`` for ``clinical``; ``batch_transform`` is applied afterwards.  Random draws come from Python's ``random``, per
+    sample in the chain's order (``random.random()`` of ``HemisphericFlip``, then ``randint`` for x, y, z of ``RandomPatch``): with
+    equal ``random`` state a batch equals the per-sample chain on the same cases bit for bit.  ``ResamplePlaneXY`` was applied
+    when the cache was filled.  ``last_table``: the host copy of the latest batch's table."""
+
+    def __init__(self, cache, items, batch_size, transforms, batch_transform=None):
+        from torch.utils.data.sampler import BatchSampler, SubsetRandomSampler
+        self._stages = _parse_chain(transforms)
+        missing = [i for i in items if i not in cache.slot_of]
+        if missing:
+            raise ValueError("CachedBatchLoader: items %r are not in the cache" % (missing,))
+        self.cache, self.dataset, self.batch_size, self.batch_transform = cache, cache.dataset, batch_size, batch_transform
+        self.sampler = SubsetRandomSampler(items)
+        self.batch_sampler = BatchSampler(self.sampler, batch_size, drop_last=False)
+        self.last_table = None
+        Z, Y, X = cache.shape_zyx
+        pad, patch = self._stages.get("PadImages"), self._stages.get("RandomPatch")
+        self._pad0 = (pad._padx, pad._pady, pad._padz) if pad is not None else (0, 0, 0)
+        self._padval0 = pad._pad_value if pad is not None else 0.0
+        self._padded = (X + 2 * self._pad0[0], Y + 2 * self._pad0[1], Z + 2 * self._pad0[2])      # what RandomPatch sees
+        if patch is not None:
+            self._ext0 = (patch._w, patch._h, patch._d)
+            self._ext1 = (patch._w - 2 * patch._padx, patch._h - 2 * patch._pady, patch._d - 2 * patch._padz)
+        else:
+            self._ext0, self._ext1 = self._padded, (X, Y, Z)
+
+    def __len__(self):
+        return len(self.batch_sampler)
+
+    def __iter__(self):
+        for items in self.batch_sampler:
+            yield self.make_batch(items)
+
+    def _row(self, item):
+        slot = self.cache.slot_of[item]
+        flip, patch = self._stages.get("flip"), self._stages.get("RandomPatch")
+        flag = 0
+        if isinstance(flip, HemisphericFlip):
+            flag = int(random.random() > 0.5)
+        elif flip is not None:
+            flag = int(self.cache.case_ids[slot] > flip.split_id)
+        origin = (0, 0, 0)
+        if patch is not None:
+            origin = tuple(random.randint(0, n - e) for n, e in zip(self._padded, self._ext0))
+        return (slot,) + origin + (flag,)
+
+    def make_batch(self, items):
+        from torch.utils.data import default_collate
+        cache = self.cache
+        table = torch.tensor([self._row(int(i)) for i in items], dtype=torch.int32)
+        self.last_table = table
+        images, labels, table_dev = _gather_launch(cache, table, self._ext0, self._pad0, self._padval0, self._ext1, (0, 0, 0))
+        slots = table[:, 0].tolist()
+        batch = {KEY_CASE_ID: default_collate([cache.case_ids[s] for s in slots]),
+                 KEY_CLINICAL_IDX: default_collate([cache.clinical_idx[s] for s in slots]),
+                 KEY_IMAGES: images, KEY_LABELS: labels,
+                 KEY_GLOBAL: cache.clinical.index_select(0, table_dev[:, 0]) if cache.clinical is not None else []}
+        return self.batch_transform(batch) if self.batch_transform is not None else batch
+
+
+def _cache_prefix(chains):
+    """the ``ResamplePlaneXY`` steps the chains start with -- they must agree, since the loaders share one cache"""
+    found = [_parse_chain(c).get("ResamplePlaneXY") for c in chains]
+    keys = set((t._scale_factor, t._order) if t is not None else None for t in found)
+    if len(keys) != 1:
+        raise ValueError("device_cache: the training and the validation chain resample differently (%r); they share one cache" % (keys,))
+    return [found[0]] if found[0] is not None else []
+
+
+def _cached_loaders(modalities, labels, chains, item_lists, batch_size, batch_transforms):
+    if not torch.cuda.is_available():
+        raise RuntimeError("device_cache=True (stroke_prediction_amd) needs a GPU: the case cache lives in device memory and the "
+                           "batches are gathered by a HIP kernel; there is no CPU path")
+    ds = _dataset(modalities, labels, _cache_prefix(chains), "cuda")
+    cache = DeviceCaseCache(ds, "cuda", items=[i for items in item_lists for i in items])
+    return [CachedBatchLoader(cache, items, batch_size, chain, bt) for chain, items, bt in zip(chains, item_lists, batch_transforms)]
+
+
 def split_data_loader3D(modalities, labels, indices, batch_size, random_seed=None, valid_size=0.5, shuffle=True,
-                        num_workers=4, pin_memory=False, train_transform=[], valid_transform=[], batch_transform=None):
+                        num_workers=4, pin_memory=False, train_transform=[], valid_transform=[], batch_transform=None,
+                        device_cache=False):
     """data.py:113-147: one fold -> (training loader, validation loader); the first ``valid_size`` share of the
     (seed-shuffled) fold validates.  ``batch_transform`` (e.g. ``BatchElasticDeform``): applied to every collated TRAINING
-    batch; the validation loader never gets it."""
+    batch; the validation loader never gets it.  ``device_cache``: both loaders are ``CachedBatchLoader``s over one shared
+    ``DeviceCaseCache`` (needs a GPU)."""
     assert 0 <= valid_size <= 1, "[!] valid_size should be in the range [0, 1]."
     assert train_transform and valid_transform, "You must provide at least a numpy-to-torch transformation."
     dev = _pipeline_device()
     ds_train, ds_valid = _dataset(modalities, labels, train_transform, dev), _dataset(modalities, labels, valid_transform, dev)
     items = _fold_items(ds_train, indices, shuffle, random_seed)
     split = int(np.floor(valid_size * len(items)))
+    if device_cache:
+        return tuple(_cached_loaders(modalities, labels, [train_transform, valid_transform], [items[split:], items[:split]], batch_size,
+                                     [batch_transform, None]))
     return (_loader(ds_train, items[split:], batch_size, num_workers, pin_memory, True, batch_transform),
             _loader(ds_valid, items[:split], batch_size, num_workers, pin_memory, False))
 
 
 def single_data_loader3D(modalities, labels, indices, batch_size, random_seed=None, valid_size=0.5, shuffle=True,
-                         num_workers=4, pin_memory=False, train_transform=[], batch_transform=None):
-    """data.py:150-172; ``batch_transform``: as for ``split_data_loader3D``."""
+                         num_workers=4, pin_memory=False, train_transform=[], batch_transform=None, device_cache=False):
+    """data.py:150-172; ``batch_transform``, ``device_cache``: as for ``split_data_loader3D``."""
     assert train_transform, "You must provide at least a numpy-to-torch transformation."
     ds = _dataset(modalities, labels, train_transform, _pipeline_device())
-    return _loader(ds, _fold_items(ds, indices, shuffle, random_seed), batch_size, num_workers, pin_memory, True, batch_transform)
+    items = _fold_items(ds, indices, shuffle, random_seed)
+    if device_cache:
+        return _cached_loaders(modalities, labels, [train_transform], [items], batch_size, [batch_transform])[0]
+    return _loader(ds, items, batch_size, num_workers, pin_memory, True, batch_transform)
 
 
 def get_stroke_shape_training_data(modalities, labels, train_transform, valid_transform, fold_indices, ratio, seed=4,
-                                   batchsize=2, split=True, batch_transform=None):
+                                   batchsize=2, split=True, batch_transform=None, device_cache=False):
     """data.py:175-182 (``num_workers=0``: the transforms run in the training process -- here on its GPU)."""
     if split:
         return split_data_loader3D(modalities, labels, fold_indices, batchsize, random_seed=seed, valid_size=ratio,
                                    train_transform=train_transform, valid_transform=valid_transform, num_workers=0,
-                                   batch_transform=batch_transform)
+                                   batch_transform=batch_transform, device_cache=device_cache)
     return single_data_loader3D(modalities, labels, fold_indices, batchsize, random_seed=seed, valid_size=ratio,
-                                train_transform=train_transform, num_workers=0, batch_transform=batch_transform), None
+                                train_transform=train_transform, num_workers=0, batch_transform=batch_transform,
+                                device_cache=device_cache), None
 
 
 get_stroke_prediction_training_data = get_stroke_shape_training_data      # data.py:185-192: the same factory

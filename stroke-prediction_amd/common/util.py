@@ -28,6 +28,9 @@ _EXPERIMENT = [
     ("--fusedadam", dict(action="store_true", default=False, help="(MI355X build) FusedAdam on the flat buffers instead of torch.optim.Adam")),
     ("--batchaugment", dict(action="store_true", default=False,
                             help="(MI355X build) CAE training: flip + elastic deformation once per collated batch (data.BatchElasticDeform)")),
+    ("--devicecache", dict(action="store_true", default=False,
+                           help="(MI355X build) upload every case once and gather each batch from the device-resident cache with one "
+                                "kernel launch (data.DeviceCaseCache / CachedBatchLoader)")),
 ]
 _CAE = [
     ("--epochs", dict(type=int, default=300, help="Number of epochs")),
@@ -73,7 +76,16 @@ class ExpParser(argparse.ArgumentParser):
 
 
 class CAEParser(ExpParser):
+    """The CAE training scripts' chains hold the per-sample ``ElasticDeform``, which cannot run from the device cache: there
+    ``--devicecache`` goes with ``--batchaugment`` (the cached whole-volume gather then feeds ``BatchElasticDeform``)."""
     EXTRA = _CAE
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.devicecache and not ns.batchaugment:
+            self.error("--devicecache needs --batchaugment here: the per-sample ElasticDeform of the CAE training chain cannot run "
+                       "from the device-resident case cache; with both flags the cached gather feeds BatchElasticDeform")
+        return ns
 
 
 class UnetParser(ExpParser):

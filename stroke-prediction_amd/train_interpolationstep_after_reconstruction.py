@@ -46,7 +46,8 @@ def train(args):
     valid_tf = common + [data.ToTensor()]
     ds_train, ds_valid = data.get_stroke_shape_training_data(IMAGE_VOLUMES, LABEL_VOLUMES, train_tf, valid_tf, args.fold,
                                                              args.validsetsize, batchsize=args.batchsize,
-                                                             batch_transform=data.BatchElasticDeform(flip="random") if args.batchaugment else None)
+                                                             batch_transform=data.BatchElasticDeform(flip="random") if args.batchaugment else None,
+                                                             device_cache=args.devicecache)
     print('Size training set:', len(ds_train.sampler.indices), 'samples | Size validation set:', len(ds_valid.sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
     learner = CaeStepLearner(ds_train, ds_valid, cae, optimizer, scheduler, n_epochs=args.epochs,

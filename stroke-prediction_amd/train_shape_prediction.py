@@ -62,7 +62,8 @@ def build_loaders(args):
     valid_tf = common + [data.ToTensor()]
     loaders = data.get_stroke_prediction_training_data(MODALITIES, LABEL_VOLUMES, train_tf, valid_tf, args.fold, args.validsetsize,
                                                        batchsize=args.batchsize,
-                                                       batch_transform=data.BatchElasticDeform(apply_to_images=True) if args.batchaugment else None)
+                                                       batch_transform=data.BatchElasticDeform(apply_to_images=True) if args.batchaugment else None,
+                                                       device_cache=args.devicecache)
     print('Size training set:', len(loaders[0].sampler.indices), 'samples | Size validation set:', len(loaders[1].sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
     return loaders

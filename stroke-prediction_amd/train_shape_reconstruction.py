@@ -57,7 +57,8 @@ def build_loaders(args):
     use_validation = not args.steplearning
     loaders = data.get_stroke_shape_training_data(IMAGE_VOLUMES, LABEL_VOLUMES, train_tf, valid_tf, args.fold, args.validsetsize,
                                                   seed=args.seed, batchsize=args.batchsize, split=use_validation,
-                                                  batch_transform=data.BatchElasticDeform(flip="random") if args.batchaugment else None)
+                                                  batch_transform=data.BatchElasticDeform(flip="random") if args.batchaugment else None,
+                                                  device_cache=args.devicecache)
     n_valid = len(loaders[1].sampler.indices) if loaders[1] is not None else 0
     print('Size training set:', len(loaders[0].sampler.indices), 'samples | Size validation set:', n_valid,
           'samples | Capacity batch:', args.batchsize, 'samples')

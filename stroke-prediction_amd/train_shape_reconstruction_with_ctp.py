@@ -62,7 +62,8 @@ def build_loaders(args):
     valid_tf = common + [data.ToTensor()]
     loaders = data.get_stroke_shape_training_data(IMAGE_VOLUMES, LABEL_VOLUMES, train_tf, valid_tf, args.fold, args.validsetsize,
                                                   seed=args.seed, batchsize=args.batchsize,
-                                                  batch_transform=data.BatchElasticDeform() if args.batchaugment else None)
+                                                  batch_transform=data.BatchElasticDeform() if args.batchaugment else None,
+                                                  device_cache=args.devicecache)
     print('Size training set:', len(loaders[0].sampler.indices), 'samples | Size validation set:', len(loaders[1].sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
     return loaders
