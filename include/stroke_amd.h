@@ -39,6 +39,10 @@ enum { SP_OK = 0, SP_EINVAL = -1, SP_EHIP = -2 };
 enum { SP_REDUCE_ROWS = 8 };
 /* row pitch (doubles) of the Dice accumulator sums[SP_REDUCE_ROWS][SP_DICE_PITCH(C)]: whole 128-byte lines */
 #define SP_DICE_PITCH(C) ((3 * (C) + 15) / 16 * 16)
+/* the voxel-loss family (sp_vloss_*: Dice and / or binary cross entropy): the terms a call evaluates, and the row pitch (doubles) of
+ * its accumulator sums[SP_REDUCE_ROWS][SP_VLOSS_PITCH(C)], four columns per channel */
+enum { SP_VLOSS_DICE = 1, SP_VLOSS_BCE = 2 };
+#define SP_VLOSS_PITCH(C) ((4 * (C) + 15) / 16 * 16)
 enum { SP_BF16 = 0, SP_F32 = 1,
        /* bf16 PAIR: value = hi + lo with hi = bf16(value) and lo = bf16(value - hi), stored as TWO bf16 tensors of the same
         * shape (the hi tensor is what the bf16 kernels of the backward pass read; the lo tensor lies lo_delta bytes behind it).
@@ -778,6 +782,40 @@ int sp_cae_loss_bwd(const float* c, int64_t cbs, const float* p, int64_t pbs, co
 /* dout (contiguous) = *upstream * (ca[c]*t + cb[c]*o); upstream: device pointer to the scalar gradient (NULL = 1) */
 int sp_dice_bwd(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* coef,
                 const float* upstream, int32_t B, int32_t C, int64_t DHW, float* dout, sp_stream_t stream);
+
+/* ------------------------------------------------------------------ BCE and Dice + BCE criteria (the `# nn.BCELoss()` the
+ * reference's training scripts name beside BatchDiceLoss, e.g. train_unet_segmentation.py:15).  torch.nn.BCELoss semantics:
+ *   bce(o, t) = -(t max(log o, -100) + (1 - t) max(log(1 - o), -100)),  d bce / d o = (o - t) / max(o (1 - o), 1e-12)
+ * so o exactly 0 or 1 (a saturated fp32 sigmoid) is legal input and gives finite values and gradients.
+ * sp_vloss_sums: o, t as for sp_dice_sums.  terms: SP_VLOSS_DICE | SP_VLOSS_BCE.  sums[row][4*c + k] (fp64, zeroed by the caller;
+ * SP_REDUCE_ROWS replica rows of SP_VLOSS_PITCH(C) doubles) += (sum o*t, sum o*o, sum t*t, sum bce) over batch and volume; the
+ * moments of a term that is not asked for are neither computed nor added.  Same reduction order as sp_dice_sums.  16-byte loads when
+ * DHW % 4 == 0 and every row base (o, t, the batch strides) is 16-byte aligned, element loads otherwise. */
+int sp_vloss_sums(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, int32_t B, int32_t C, int64_t DHW,
+                  int32_t terms, double* sums, sp_stream_t stream);
+/* loss = [w_dice ? 1 - sum_c wd_c (2 I_c + eps)/(O_c + T_c + eps) : 0] + [w_bce ? sum_c wb_c S_c / count : 0]; either weight vector
+ * ([C], device) may be NULL = the term is absent.  count: elements per channel behind the sums (B * DHW, times the world size when
+ * the sums were all-reduced).  coef[3c .. 3c+2] = (ca, cb, cc): d loss / d o = ca*t + cb*o + cc*(o - t)/max(o(1 - o), 1e-12).
+ * The replica rows are zeroed again after they are read, as by sp_dice_finalize_clear. */
+int sp_vloss_finalize_clear(double* sums, const float* w_dice, const float* w_bce, double eps, double count, int32_t C, float* loss,
+                            float* coef, sp_stream_t stream);
+/* dout (dense (B, C, DHW)) = *upstream * (ca[c]*t + cb[c]*o + cc[c]*(o - t)/max(o(1 - o), 1e-12)); upstream: device pointer to the
+ * scalar gradient (NULL = 1).  Channels with cc == 0 skip the division. */
+int sp_vloss_bwd(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* coef, const float* upstream,
+                 int32_t B, int32_t C, int64_t DHW, float* dout, sp_stream_t stream);
+/* sp_cae_loss_fwd / _bwd with the criterion chosen by terms: each of the three criterion terms (core, penumbra, lesion) is
+ *   [SP_VLOSS_DICE] (1 - dice_weight (2 I + eps)/(O + T + eps)) + [SP_VLOSS_BCE] bce_weight * mean bce
+ * the hinge terms, the latent term and the / (5 + factor) are those of sp_cae_loss_fwd.  sums: SP_REDUCE_ROWS x 16 doubles, zeroed by
+ * the caller (columns 0-11 as for sp_cae_loss_fwd, 12-14 the BCE sums of c, p, l); coef: 11 floats (0-7 as for sp_cae_loss_fwd,
+ * 8-10 the cc of c, p, l).  Three launches: sums, finalize, backward. */
+int sp_cae_loss_crit_fwd(const float* c, int64_t cbs, const float* p, int64_t pbs, const float* l, int64_t lbs, const float* i, int64_t ibs,
+                         const float* tc, int64_t tcbs, const float* tp, int64_t tpbs, const float* tl, int64_t tlbs, int32_t B, int64_t DHW,
+                         const float* zi, const float* zl, int64_t nlat, float dice_weight, float bce_weight, int32_t terms, double eps,
+                         float factor, double* sums, float* loss, float* coef, sp_stream_t stream);
+int sp_cae_loss_crit_bwd(const float* c, int64_t cbs, const float* p, int64_t pbs, const float* l, int64_t lbs, const float* i, int64_t ibs,
+                         const float* tc, int64_t tcbs, const float* tp, int64_t tpbs, const float* tl, int64_t tlbs, int32_t B, int64_t DHW,
+                         const float* coef, const float* up, float* dc, float* dp, float* dl, float* di, const float* zi, const float* zl,
+                         int64_t nlat, float* dzi, float* dzl, sp_stream_t stream);
 
 /* ------------------------------------------------------------------ fused classify head (Unet3D.py:49-54,75-77)
  * seg = sigmoid(W2 * lrelu(W1*x + b1) + b2): x channels-last [B*nvox][CP], seg NCDHW fp32 [B][NC][nvox].

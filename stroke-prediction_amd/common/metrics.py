@@ -7,6 +7,10 @@ sensitivity, specificity, Hausdorff distance and ASSD as ``medpy.metric.binary``
 ``sp_confusion_counts`` and ``sp_surface_distances`` (border extraction + exact Euclidean distance transform), or -- T results
 against one target, the points of a time-to-treatment curve -- ``sp_binary_measures_many`` in one enqueue.  There is
 no host implementation here; the checker is ``oracle/measures.py``.
+
+``BCELoss`` and ``DiceBCELoss`` -- the ``# nn.BCELoss()`` the reference's training scripts name beside their Dice criterion -- run on
+one kernel family of their own (``sp_vloss_sums`` / ``_finalize_clear`` / ``_bwd``), take the same fused routes as ``BatchDiceLoss``
+(``mean_of_channel_losses``, ``cae_reconstruction_loss``) and are picked by name with ``make_criterion``.
 """
 import numpy
 import torch
@@ -135,6 +139,128 @@ class BatchDiceLoss(LossModule):
         return _DiceFn.apply(outputs, targets, tuple(float(w) for w in self._label_weights), float(self._epsilon))
 
 
+_VLOSS_SUMS = {}     # (device, C, stream) -> [replica rows of the voxel-loss sums (zero between calls), busy]
+
+
+class _VoxelLossFn(torch.autograd.Function):
+    """loss = [1 - sum_c wd_c (2 I_c + eps) / (O_c + T_c + eps)] + [sum_c wb_c mean_c bce(o, t)], either bracket absent when its
+    weights are None; sums and means over batch and volume per channel, bce with torch.nn.BCELoss semantics.  Shaped like _DiceFn:
+    two HIP launches forward (sums, finalize) and one backward.  In the exact data-parallel mode the sums are all-reduced and the
+    element count is the global one: the local backward yields this rank's share of the whole-batch gradient (as _GlobalMeanFn)."""
+
+    @staticmethod
+    def forward(ctx, outputs, targets, w_dice, w_bce, eps):
+        from stroke_prediction_amd.runtime import lib as L, ops as O
+        from stroke_prediction_amd.runtime.layers import SYNC, _allreduce
+        o, obs = _batch_strided(outputs)
+        t, tbs = _batch_strided(targets)
+        B, C = o.shape[0], o.shape[1]
+        dhw = o.numel() // (B * C)
+        terms = (L.SP_VLOSS_DICE if w_dice is not None else 0) | (L.SP_VLOSS_BCE if w_bce is not None else 0)
+        # one accumulator per (device, C, stream), left zero by sp_vloss_finalize_clear; ``busy`` as in _DiceFn
+        key = (o.device, C, int(torch.cuda.current_stream(o.device).cuda_stream))
+        ent = _VLOSS_SUMS.get(key)
+        if ent is None or ent[1]:
+            ent = _VLOSS_SUMS[key] = [torch.zeros(L.SP_REDUCE_ROWS, L.SP_VLOSS_PITCH(C), dtype=torch.float64, device=o.device), False]
+        sums = ent[0]
+        ent[1] = True
+        L.call("sp_vloss_sums", O.ptr(o), obs, O.ptr(t), tbs, B, C, dhw, terms, O.ptr(sums), O.stream())
+        count = float(B * dhw)
+        if SYNC["on"]:                  # whole-batch sums and a whole-batch mean
+            _allreduce(sums)
+            count *= SYNC["world"]
+        wd = None if w_dice is None else _weights_on(o.device, w_dice)      # cached: no host->device copy inside a captured step
+        wb = None if w_bce is None else _weights_on(o.device, w_bce)
+        loss = torch.empty((), dtype=torch.float32, device=o.device)
+        coef = torch.empty(3 * C, dtype=torch.float32, device=o.device)
+        L.call("sp_vloss_finalize_clear", O.ptr(sums), None if wd is None else O.ptr(wd), None if wb is None else O.ptr(wb), float(eps),
+               count, C, O.ptr(loss), O.ptr(coef), O.stream())
+        ent[1] = False
+        ctx.save_for_backward(o, t, coef)
+        ctx.strides = (obs, tbs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        from stroke_prediction_amd.runtime import lib as L, ops as O
+        o, t, coef = ctx.saved_tensors
+        obs, tbs = ctx.strides
+        B, C = o.shape[0], o.shape[1]
+        up = gloss if (gloss.dtype == torch.float32 and gloss.is_contiguous()) else gloss.float().contiguous()
+        d = torch.empty(o.shape, dtype=torch.float32, device=o.device)
+        L.call("sp_vloss_bwd", O.ptr(o), obs, O.ptr(t), tbs, O.ptr(coef), O.ptr(up), B, C, o.numel() // (B * C), O.ptr(d), O.stream())
+        return d, None, None, None, None
+
+
+def _check_voxel_loss_inputs(name, outputs, targets, label_weights):
+    assert label_weights is None or targets.shape[1] == len(label_weights), \
+        'Ground truth number of labels does not match with label weight vector'
+    assert outputs.shape == targets.shape
+    if not outputs.is_cuda:
+        raise RuntimeError("%s (stroke_prediction_amd) runs on the GPU with channel dim 1 only" % name)
+
+
+class BCELoss(LossModule):
+    """``torch.nn.BCELoss()`` on (B, C, ...) GPU tensors (channel dim 1): sum_c w_c mean_c bce.  The default weights, 1 / C each, are
+    the mean over everything."""
+
+    def __init__(self, label_weights=None):
+        super(BCELoss, self).__init__()
+        self._label_weights = label_weights
+        self._dim = 1
+
+    def weights(self, C):
+        if self._label_weights is None:
+            return (1.0 / C,) * C
+        return tuple(float(w) for w in self._label_weights)
+
+    def forward(self, outputs, targets):
+        _check_voxel_loss_inputs("BCELoss", outputs, targets, self._label_weights)
+        return _VoxelLossFn.apply(outputs, targets, None, self.weights(outputs.shape[1]), 0.0)
+
+
+class DiceBCELoss(LossModule):
+    """``BatchDiceLoss(label_weights, epsilon)(o, t) + bce_weight * BCELoss()(o, t)`` in one sums / finalize / backward set."""
+
+    def __init__(self, label_weights, bce_weight=1.0, epsilon=0.0000001):
+        super(DiceBCELoss, self).__init__()
+        self._label_weights = label_weights
+        self._bce_weight = bce_weight
+        self._epsilon = epsilon
+        self._dim = 1
+
+    def forward(self, outputs, targets):
+        _check_voxel_loss_inputs("DiceBCELoss", outputs, targets, self._label_weights)
+        C = outputs.shape[1]
+        return _VoxelLossFn.apply(outputs, targets, tuple(float(w) for w in self._label_weights),
+                                  (float(self._bce_weight) / C,) * C, float(self._epsilon))
+
+
+def _single_label_terms(criterion):
+    """(Dice weight or None, BCE weight or None, eps) of a criterion that weighs ONE label class -- what the fused routes below
+    evaluate per channel / per reconstruction --, or None for anything else."""
+    if getattr(criterion, "_dim", None) != 1:
+        return None
+    if isinstance(criterion, BatchDiceLoss) and len(criterion._label_weights) == 1:
+        return float(criterion._label_weights[0]), None, float(criterion._epsilon)
+    if isinstance(criterion, BCELoss) and (criterion._label_weights is None or len(criterion._label_weights) == 1):
+        return None, criterion.weights(1)[0], 0.0
+    if isinstance(criterion, DiceBCELoss) and len(criterion._label_weights) == 1:
+        return float(criterion._label_weights[0]), float(criterion._bce_weight), float(criterion._epsilon)
+    return None
+
+
+def make_criterion(name):
+    """The training scripts' ``--criterion``: ``dice`` (the reference's choice), ``bce`` (the one its comment names), ``dicebce``."""
+    if name == "dice":
+        return BatchDiceLoss([1.0])
+    if name == "bce":
+        return BCELoss()
+    if name == "dicebce":
+        return DiceBCELoss([1.0])
+    raise ValueError("criterion %r: one of dice, bce, dicebce" % (name,))
+
+
 class _CaeLossFn(torch.autograd.Function):
     """CaeReconstructionLearner.loss_step (reference :52-70) as three HIP launches (sp_cae_loss_fwd / _bwd) instead of ~60 torch and
     Dice kernels: [ mean(|p-i|-(p-i)) + mean(|p-c|-(p-c)) + Dice(c) + Dice(p) + Dice(l) + f mean|zi - zl| ] / (5 + f).  The four
@@ -142,8 +268,9 @@ class _CaeLossFn(torch.autograd.Function):
     call that produced them stacked on the batch axis (Cae3D._StackManyFn) takes the buffer as it is."""
 
     @staticmethod
-    def forward(ctx, c, p, l, i, tc, tp, tl, zi, zl, factor, weight, eps):
+    def forward(ctx, c, p, l, i, tc, tp, tl, zi, zl, factor, weight, eps, bce_weight=None):
         from stroke_prediction_amd.runtime import lib as L, ops as O
+        crit = bce_weight is not None            # BCELoss / DiceBCELoss: sp_cae_loss_crit_* (weight None = no Dice term)
         recs = [_batch_strided(t) for t in (c, p, l, i)]
         gts = [_batch_strided(t) for t in (tc, tp, tl)]
         zi_, zl_ = zi.contiguous().float(), zl.contiguous().float()
@@ -152,12 +279,18 @@ class _CaeLossFn(torch.autograd.Function):
         dev = c.device
         sums = torch.zeros(L.SP_REDUCE_ROWS, 16, dtype=torch.float64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        coef = torch.empty(8, dtype=torch.float32, device=dev)
+        coef = torch.empty(11 if crit else 8, dtype=torch.float32, device=dev)
         args = []
         for t, bs in recs + gts:
             args += [O.ptr(t), bs]
-        L.call("sp_cae_loss_fwd", *args, B, dhw, O.ptr(zi_), O.ptr(zl_), zi_.numel(), float(weight), float(eps), float(factor),
-               O.ptr(sums), O.ptr(loss), O.ptr(coef), O.stream())
+        if crit:
+            L.call("sp_cae_loss_crit_fwd", *args, B, dhw, O.ptr(zi_), O.ptr(zl_), zi_.numel(), float(weight or 0.0), float(bce_weight),
+                   (L.SP_VLOSS_DICE if weight is not None else 0) | L.SP_VLOSS_BCE, float(eps), float(factor), O.ptr(sums), O.ptr(loss), O.ptr(coef),
+                   O.stream())
+        else:
+            L.call("sp_cae_loss_fwd", *args, B, dhw, O.ptr(zi_), O.ptr(zl_), zi_.numel(), float(weight), float(eps), float(factor),
+                   O.ptr(sums), O.ptr(loss), O.ptr(coef), O.stream())
+        ctx.crit = crit
         ctx.save_for_backward(*[t for t, _ in recs + gts], zi_, zl_, coef)
         ctx.strides = [bs for _, bs in recs + gts]
         ctx.shapes = (tuple(c.shape), tuple(zi.shape), tuple(zl.shape))
@@ -180,9 +313,9 @@ class _CaeLossFn(torch.autograd.Function):
         args = []
         for t, bs in zip(ts, ctx.strides):
             args += [O.ptr(t), bs]
-        L.call("sp_cae_loss_bwd", *args, B, dhw, O.ptr(coef), O.ptr(up), O.ptr(d[0]), O.ptr(d[1]), O.ptr(d[2]), O.ptr(d[3]),
-               O.ptr(zi_), O.ptr(zl_), zi_.numel(), O.ptr(dzi), O.ptr(dzl), O.stream())
-        return d[0], d[1], d[2], d[3], None, None, None, dzi.view(ctx.shapes[1]), dzl.view(ctx.shapes[2]), None, None, None
+        L.call("sp_cae_loss_crit_bwd" if ctx.crit else "sp_cae_loss_bwd", *args, B, dhw, O.ptr(coef), O.ptr(up), O.ptr(d[0]), O.ptr(d[1]),
+               O.ptr(d[2]), O.ptr(d[3]), O.ptr(zi_), O.ptr(zl_), zi_.numel(), O.ptr(dzi), O.ptr(dzl), O.stream())
+        return d[0], d[1], d[2], d[3], None, None, None, dzi.view(ctx.shapes[1]), dzl.view(ctx.shapes[2]), None, None, None, None
 
 
 def cae_reconstruction_loss(rec, gt, lat, factor, criterion):
@@ -191,12 +324,13 @@ def cae_reconstruction_loss(rec, gt, lat, factor, criterion):
     import os
     from stroke_prediction_amd.runtime.layers import SYNC
     ts = (rec.core, rec.penu, rec.lesion, rec.interpolation, gt.core, gt.penu, gt.lesion)
-    if os.environ.get("SP_CAE_FUSED_LOSS", "1") == "0" or SYNC["on"] or not isinstance(criterion, BatchDiceLoss) or len(criterion._label_weights) != 1 \
-            or criterion._dim != 1 or any(t is None or not t.is_cuda or t.dim() != 5 or t.shape[1] != 1 or t.shape != ts[0].shape for t in ts) \
+    terms = _single_label_terms(criterion)       # BatchDiceLoss -> sp_cae_loss_fwd, BCELoss / DiceBCELoss -> sp_cae_loss_crit_fwd
+    if os.environ.get("SP_CAE_FUSED_LOSS", "1") == "0" or SYNC["on"] or terms is None or any(t is None or not t.is_cuda or t.dim() != 5 or t.shape[1] != 1 or t.shape != ts[0].shape for t in ts) \
             or lat.interpolation is None or lat.lesion is None or lat.interpolation.shape != lat.lesion.shape:
         return None
+    w_dice, w_bce, eps = terms
     return _CaeLossFn.apply(rec.core, rec.penu, rec.lesion, rec.interpolation, gt.core.float(), gt.penu.float(), gt.lesion.float(),
-                            lat.interpolation, lat.lesion, float(factor), float(criterion._label_weights[0]), float(criterion._epsilon))
+                            lat.interpolation, lat.lesion, float(factor), w_dice, eps, w_bce)
 
 
 def _stacked_base(parts):
@@ -220,14 +354,17 @@ def mean_of_channel_losses(criterion, outputs, targets):
     consecutive channel slices of one segmentation tensor and one label tensor (what Unet3D.forward / UnetInference
     produce), this is BatchDiceLoss over n channels with weights w/n: evaluated in one sums / finalize / backward
     launch on the base tensors, and the gradient lands on the segmentation directly (no slice-backward zero-fill,
-    copy and add per channel).  Anything else: the literal sum of calls."""
+    copy and add per channel).  A single-label BCELoss (weights 1/n) or DiceBCELoss (Dice weights w/n, BCE weights
+    bce_weight/n) takes the same route on the sp_vloss_* kernels.  Anything else: the literal sum of calls."""
     n = len(outputs)
-    if isinstance(criterion, BatchDiceLoss) and len(criterion._label_weights) == 1 and criterion._dim == 1 and n > 1 \
-            and outputs[0].is_cuda:
+    terms = _single_label_terms(criterion)
+    if terms is not None and n > 1 and outputs[0].is_cuda:
         ob, tb = _stacked_base(outputs), _stacked_base(targets)
         if ob is not None and tb is not None:
-            w = float(criterion._label_weights[0]) / n
-            return _DiceFn.apply(ob, tb, (w,) * n, float(criterion._epsilon))
+            w_dice, w_bce, eps = terms
+            if w_bce is None:
+                return _DiceFn.apply(ob, tb, (w_dice / n,) * n, eps)
+            return _VoxelLossFn.apply(ob, tb, None if w_dice is None else (w_dice / n,) * n, (w_bce / n,) * n, eps)
     total = criterion(outputs[0], targets[0])
     for o, t in zip(outputs[1:], targets[1:]):
         total = total + criterion(o, t)

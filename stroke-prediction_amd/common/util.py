@@ -31,6 +31,9 @@ _EXPERIMENT = [
     ("--devicecache", dict(action="store_true", default=False,
                            help="(MI355X build) upload every case once and gather each batch from the device-resident cache with one "
                                 "kernel launch (data.DeviceCaseCache / CachedBatchLoader)")),
+    ("--criterion", dict(type=str, default="dice", choices=["dice", "bce", "dicebce"],
+                         help="(MI355X build) training criterion (metrics.make_criterion): BatchDiceLoss([1.0]) as the reference, the "
+                              "nn.BCELoss() its scripts name as the alternative, or their sum")),
 ]
 _CAE = [
     ("--epochs", dict(type=int, default=300, help="Number of epochs")),

@@ -94,6 +94,13 @@ BnFinArgs, BnBwdArgs, ConvArgs, WgradArgs, WgradF8Args, ConvFcArgs, Conv3dDesc, 
 # the elementwise kernels reduce into
 SP_BF16, SP_F32, SP_HL, SP_REDUCE_ROWS = (CONSTS[n] for n in ("SP_BF16", "SP_F32", "SP_HL", "SP_REDUCE_ROWS"))
 ACT_NONE, ACT_LEAKY, ACT_ELU, ACT_SIGMOID = (CONSTS["SP_ACT_" + n] for n in ("NONE", "LEAKY", "ELU", "SIGMOID"))
+SP_VLOSS_DICE, SP_VLOSS_BCE = CONSTS["SP_VLOSS_DICE"], CONSTS["SP_VLOSS_BCE"]      # the terms of the sp_vloss_* / sp_cae_loss_crit_* calls
+
+
+def SP_VLOSS_PITCH(C):
+    """row pitch (doubles) of the sp_vloss_* accumulator: the header's macro of that name (the parser drops preprocessor lines)"""
+    return (4 * C + 15) // 16 * 16
+
 
 # precision modes of the models (``Unet3D(dtype=...)``, ``Enc3D(dtype=...)``) -> storage type of the engine's tensors
 DTYPE_CODES = {"bf16": SP_BF16, "f32": SP_F32, "fp8": SP_BF16, "fp8b": SP_BF16, "f16": SP_BF16, "bf16x3": SP_BF16, "f16x3": SP_BF16}

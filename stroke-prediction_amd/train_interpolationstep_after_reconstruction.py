@@ -52,7 +52,7 @@ def train(args):
           'samples | Capacity batch:', args.batchsize, 'samples')
     learner = CaeStepLearner(ds_train, ds_valid, cae, optimizer, scheduler, n_epochs=args.epochs,
                              path_previous_base=args.inbasepath, path_outputs_base=args.outbasepath,
-                             criterion=metrics.BatchDiceLoss([1.0]), verbose=False)
+                             criterion=metrics.make_criterion(args.criterion), verbose=False)
     learner.run_training()
     return learner
 

@@ -75,7 +75,7 @@ def train(args):
     ds_train, ds_valid = build_loaders(args)
     learner = CaePredictionLearner(ds_train, ds_valid, cae, enc, optimizer, scheduler, n_epochs=args.epochs,
                                    path_previous_base=args.inbasepath, path_outputs_base=args.outbasepath,
-                                   criterion=metrics.BatchDiceLoss([1.0]))
+                                   criterion=metrics.make_criterion(args.criterion))
     learner.run_training()
     return learner
 

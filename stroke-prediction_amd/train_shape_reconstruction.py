@@ -71,7 +71,7 @@ def train(args):
     ds_train, ds_valid = build_loaders(args)
     learner = CaeReconstructionLearner(ds_train, ds_valid, cae, optimizer, scheduler, n_epochs=args.epochs,
                                        path_previous_base=args.inbasepath, path_outputs_base=args.outbasepath,
-                                       criterion=metrics.BatchDiceLoss([1.0]), normalization_hours_penumbra=args.normalize,
+                                       criterion=metrics.make_criterion(args.criterion), normalization_hours_penumbra=args.normalize,
                                        graph=args.graph)
     learner.run_training()
     return learner

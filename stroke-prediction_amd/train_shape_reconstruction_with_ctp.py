@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Phase-1 shape training of the CTP-conditioned CAE on the MI355X path: what the reference's
 ``train_shape_reconstruction_with_ctp.py:8-69`` sets up -- ``Cae3DCtp(Enc3DCtp, Dec3D)`` trained by ``CaeReconstructionLearner``
-with Adam(lr 1e-3, betas (0.99, 0.999), weight decay 1e-5) [+ MultiStepLR] and ``BatchDiceLoss([1.0])``, on the CBV / TTD
+with Adam(lr 1e-3, betas (0.99, 0.999), weight decay 1e-5) [+ MultiStepLR] and ``BatchDiceLoss([1.0])`` (``--criterion`` picks another), on the CBV / TTD
 modalities padded by ``--padding`` next to the core / penumbra / lesion labels -- with the same flags (``common/util.py``).
 The reference script cannot run as written: it passes ``leakage=`` (here ``alpha=0.01``) and its inference never hands the
 perfusion maps to the encoder (here ``CaeInference`` does, for models that declare ``USES_CTP_INPUTS``).  Added here:
@@ -77,7 +77,7 @@ def train(args):
     ds_train, ds_valid = build_loaders(args)
     learner = CaeReconstructionLearner(ds_train, ds_valid, cae, optimizer, scheduler, n_epochs=args.epochs,
                                        path_previous_base=args.inbasepath, path_outputs_base=args.outbasepath,
-                                       criterion=metrics.BatchDiceLoss([1.0]), normalization_hours_penumbra=args.normalize,
+                                       criterion=metrics.make_criterion(args.criterion), normalization_hours_penumbra=args.normalize,
                                        graph=args.graph)
     learner.run_training()
     return learner

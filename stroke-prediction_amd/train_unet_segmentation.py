@@ -51,7 +51,7 @@ def train(args):
         optimizer = torch.optim.Adam(params, **hyper)
     scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, args.lrsteps) if args.lrsteps else None
     ds_train, ds_valid = build_loaders(args)
-    learner = UnetSegmentationLearner(ds_train, ds_valid, unet, optimizer, scheduler, args.epochs, metrics.BatchDiceLoss([1.0]),
+    learner = UnetSegmentationLearner(ds_train, ds_valid, unet, optimizer, scheduler, args.epochs, metrics.make_criterion(args.criterion),
                                       path_previous_base=args.inbasepath, path_outputs_base=args.outbasepath, graph=args.graph)
     learner.run_training()
     best = learner.path('save', learner.FNB_MODEL)

@@ -1,0 +1,114 @@
+"""The training criteria on the device (``--criterion {dice,bce,dicebce}``): loss forward + backward per call.
+
+1. The U-Net side, a segmentation and a label tensor of 4 x 2 x 88^3: ``BatchDiceLoss([1, 1])`` (``sp_dice_*``, the path every training
+   took before the flag), ``BCELoss()`` and ``DiceBCELoss([1, 1])`` (``sp_vloss_*``), and ``torch.nn.BCELoss()`` on the same tensors.
+2. The CAE reconstruction loss at 4 x 1 x 28 x 128^2 under ``make_criterion("bce")``: the fused route (``sp_cae_loss_crit_fwd`` /
+   ``_bwd``) against the composed one (``SP_CAE_FUSED_LOSS=0``: torch operators and three criterion calls).
+
+One process; every path is warmed up, then the paths are timed alternately in windows, the device synchronised before every clock
+read; microseconds per call (median over the windows, min, max) and the bytes each path has to move over its time are printed.
+
+    python tools/bench_criteria.py [--reps N] [--windows K] [--once]
+
+``--once``: one call per path after the warm-up, no timing -- the run to put under ``rocprofv3 --kernel-trace --stats`` for the launch
+counts (markers on stdout say which path ran)."""
+import argparse
+import os
+import statistics
+import sys
+import time
+from types import SimpleNamespace as NS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+import stroke_prediction_amd  # noqa: E402,F401
+from common import metrics  # noqa: E402
+
+
+def timed(paths, reps, windows, once, bytes_moved):
+    sync = torch.cuda.synchronize
+    for _, f in paths:      # warm-up: accumulators, cached weights, code objects
+        f(); f()
+    sync()
+    if once:
+        for n, f in paths:
+            f()
+            sync()
+            print("ran %s once" % n)
+        return
+    us = {n: [] for n, _ in paths}
+    for _ in range(windows):
+        for n, f in paths:      # alternate the paths window by window
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                f()
+            sync()
+            us[n].append((time.perf_counter() - t0) / reps * 1e6)
+    for n, v in us.items():
+        med = statistics.median(v)
+        print("%-22s per call: median %8.1f us, min %8.1f, max %8.1f   (%.0f MB to move: %.2f TB/s at the median)"
+              % (n, med, min(v), max(v), bytes_moved / 1e6, bytes_moved / med / 1e6))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200, help="calls per timing window")
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--once", action="store_true")
+    args = ap.parse_args()
+    dev = "cuda:0"
+    g = torch.Generator().manual_seed(0)
+
+    # ---- 1. the U-Net side: loss forward + backward on the segmentation tensor
+    shape = (4, 2, 88, 88, 88)
+    seg = torch.rand(*shape, generator=g).to(dev).requires_grad_(True)
+    lab = (torch.rand(*shape, generator=g) > 0.7).float().to(dev)
+
+    def fwd_bwd(crit):
+        def f():
+            seg.grad = None
+            crit(seg, lab).backward()
+        return f
+    paths = [("dice (sp_dice_*)", fwd_bwd(metrics.BatchDiceLoss([1.0, 1.0]))),
+             ("bce (sp_vloss_*)", fwd_bwd(metrics.BCELoss())),
+             ("dicebce (sp_vloss_*)", fwd_bwd(metrics.DiceBCELoss([1.0, 1.0]))),
+             ("torch.nn.BCELoss", fwd_bwd(torch.nn.BCELoss()))]
+    print("loss forward + backward, segmentation %s fp32" % "x".join(map(str, shape)))
+    # the algorithm's traffic: o and t read by the sums, o and t read and the gradient written by the backward
+    timed(paths, args.reps, args.windows, args.once, 5 * 4 * seg.numel())
+
+    # ---- 2. the CAE reconstruction loss: fused against composed
+    B, dims = 4, (28, 128, 128)
+    stacked = torch.rand(4 * B, 1, *dims, generator=g).to(dev).requires_grad_(True)
+    gts = [(torch.rand(B, 1, *dims, generator=g) > 0.6).float().to(dev) for _ in range(3)]
+    zi = torch.randn(B, 200, 1, 8, 8, generator=g).to(dev).requires_grad_(True)
+    zl = torch.randn(B, 200, 1, 8, 8, generator=g).to(dev).requires_grad_(True)
+    crit = metrics.make_criterion("bce")
+    factor = 0.36
+
+    def cae(fused):
+        def f():
+            os.environ["SP_CAE_FUSED_LOSS"] = "1" if fused else "0"
+            for t in (stacked, zi, zl):
+                t.grad = None
+            parts = [stacked[k * B:(k + 1) * B] for k in range(4)]
+            rec = NS(core=parts[0], penu=parts[1], lesion=parts[2], interpolation=parts[3])
+            gt = NS(core=gts[0], penu=gts[1], lesion=gts[2])
+            loss = metrics.cae_reconstruction_loss(rec, gt, NS(interpolation=zi, lesion=zl), factor, crit)
+            assert (loss is not None) == fused
+            if loss is None:      # CaeReconstructionLearner.loss_step
+                d1, d2 = rec.penu - rec.interpolation, rec.penu - rec.core
+                loss = (torch.mean(torch.abs(d1) - d1) + torch.mean(torch.abs(d2) - d2) + crit(rec.core, gt.core) + crit(rec.penu, gt.penu)
+                        + crit(rec.lesion, gt.lesion) + factor * torch.mean(torch.abs(zi - zl))) / (5 + factor)
+            loss.backward()
+        return f
+    print("CAE reconstruction loss forward + backward under bce, reconstructions %dx1x%s fp32" % (B, "x".join(map(str, dims))))
+    # four reconstructions and three ground truths read twice, four gradients written
+    timed([("fused (crit_fwd/_bwd)", cae(True)), ("composed", cae(False))], max(1, args.reps // 4), args.windows, args.once,
+          (7 * 2 + 4) * 4 * B * dims[0] * dims[1] * dims[2])
+
+
+if __name__ == "__main__":
+    main()
