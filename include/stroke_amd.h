@@ -943,6 +943,28 @@ int sp_elastic_warp_batch(const float* src0, float* dst0, int32_t C0, const floa
 int sp_patch_gather_batch(const float* src0, float* dst0, int32_t C0, const int32_t* ext0, const int32_t* pad0, float padval0,
                           const float* src1, float* dst1, int32_t C1, const int32_t* ext1, const int32_t* pad1, float padval1,
                           const int32_t* table, int32_t N, int32_t B, int32_t Z, int32_t Y, int32_t X, sp_stream_t stream);
+/* The gather read through a per-sample transform (common/data.py: PatchAugment; csrc/sp_sample.hip): affine, elastic and intensity
+ * augmentation of a cached batch in the ONE launch that builds it.  src_t, dst_t, C_t, ext_t, pad_t, table, N, B, Z, Y, X: as for
+ * sp_patch_gather_batch (origins in group 0's padded coordinates); ext0 / pad0 are required also when C0 = 0: they are the patch
+ * frame.  Group 1's pad value is 0.
+ * xform (device, float[B][16], required): M[9] (row-major 3x3, rows x, y, z: the output -> source map), t[3], alpha_xy, alpha_z,
+ * two reserved words.  fields (device or NULL): (B, 3, d0, h0, w0), components (fx, fy, fz) on group 0's OUTPUT grid, one triple per
+ * sample shared by every channel of both groups.  intensity (device or NULL): (B, C0, 2) = (gain, bias), group 0 only.
+ * For group t and output voxel v = (x, y, z):  p = v + (pad0 - pad_t) (patch-frame position; group 0: p = v),  c = (ext0 - 1) / 2,
+ *   q = (o - pad0) + c + M (p - c) + t + (alpha_xy fx, alpha_xy fy, alpha_z fz)[b, p]     (unpadded cache coordinates),
+ * flip: q.x <- (X - 1) - q.x.  The value is the trilinear sum over the corners floor(q) + {0, 1}^3, a corner outside the volume
+ * contributing w_k padval_t: scipy.ndimage.map_coordinates(order=1, mode="grid-constant", cval=padval).  With S = sum of w_k src_k
+ * and W = sum of w_k over the corners INSIDE, group 0 writes gain S + bias W + padval0 (1 - W) (gain 1, bias 0 without intensity:
+ * padding never takes the intensity change); group 1 writes S when thresh1 < 0, else 1.0 where S >= thresh1 and 0.0 elsewhere.  A
+ * case outside [0, N) yields pad everywhere.  q is summed left to right in fp32: integers and half-integer centres are exact and
+ * weights 1 and 0 reproduce the source value, so M = I, t = 0, no fields, no intensity, thresh1 < 0 equals sp_patch_gather_batch
+ * bit for bit.  Stores as in the gather (16 bytes where w_t % 4 == 0 and dst_t is aligned).  SP_EINVAL: what the gather rejects;
+ * a NULL xform; NULL ext0 / pad0; fields given while a voxel of group 1 falls off group 0's grid (pad0 - pad1 < 0 or
+ * ext1 + (pad0 - pad1) > ext0 on an axis); intensity given with C0 = 0. */
+int sp_patch_sample_batch(const float* src0, float* dst0, int32_t C0, const int32_t* ext0, const int32_t* pad0, float padval0,
+                          const float* src1, float* dst1, int32_t C1, const int32_t* ext1, const int32_t* pad1, float thresh1,
+                          const int32_t* table, const float* xform, const float* fields, const float* intensity,
+                          int32_t N, int32_t B, int32_t Z, int32_t Y, int32_t X, sp_stream_t stream);
 
 /* ------------------------------------------------------------------ surface distances of the batch metrics
  * metrics.py:42-44 -> medpy 0.3.0 metric.binary.hd / assd (__surface_distances): border = mask XOR binary_erosion(mask)

@@ -13,7 +13,9 @@ reproduces the reference's augmentation; ``ElasticDeform(device_noise=True)`` dr
 ``BatchElasticDeform`` is the batch-level form: flip + elastic deformation of a whole collated batch in five launches
 (csrc/sp_augment.hip), handed to the loader factories as ``batch_transform``.  ``device_cache=True`` on the factories keeps
 every case on the device (``DeviceCaseCache``) and builds each batch -- flip, padding, patch, layout, stack -- with one launch of
-``sp_patch_gather_batch`` (csrc/sp_gather.hip; ``CachedBatchLoader``).
+``sp_patch_gather_batch`` (csrc/sp_gather.hip; ``CachedBatchLoader``).  ``PatchAugment`` (``patch_augment=`` on the factories) makes
+that launch ``sp_patch_sample_batch`` (csrc/sp_sample.hip): rotation, scaling, elastic deformation and an intensity change per
+sample, images and labels through one field, in the kernel that builds the batch.
 """
 import datetime
 import random
@@ -615,6 +617,125 @@ def _gather_launch(cache, table, ext0, pad0, padval0, ext1, pad1):
     return (dst0 if dst0 is not None else []), (dst1 if dst1 is not None else []), table_dev
 
 
+class PatchAugment(object):
+    """Per-sample augmentation of the patches a ``CachedBatchLoader`` cuts, applied INSIDE the launch that builds the batch
+    (``sp_patch_sample_batch``, csrc/sp_sample.hip): the cache is read through an output -> source map instead of at an origin, so a
+    rotation pulls in the voxels outside the patch and images (the padded patch) and labels (its valid-convolution crop) move through
+    the same map although their extents differ.
+
+    Per sample: with ``p_affine`` a rotation about the z axis by an angle in +-``rotate_deg`` and one in-plane scale ``s`` in
+    ``scale`` -- ``M = (1 / s) R(angle)`` on the (x, y) block and 1 on z (thick slices: no out-of-plane rotation, z is not scaled);
+    with ``p_elastic`` the displacement of ``ElasticDeform`` / ``BatchElasticDeform`` (uniform noise in [-1, 1), Gaussian filter
+    ``sigma``, scaled by ``alpha`` in plane and ``0.22 alpha`` along z) on the image patch's grid, one field triple shared by all
+    channels of both groups; with ``p_intensity`` a gain in ``gain`` and a bias in ``bias`` per image channel (padding keeps its
+    value).  ``label_threshold``: labels are 1.0 where the interpolated value reaches it, else 0.0 (``None``: left interpolated).
+
+    Every host draw comes from this object's own ``numpy.random.RandomState(seed)`` -- the same number of draws per batch whatever
+    the tosses say -- never from Python's ``random``: the loader's origin and flip draws stay where they are.  The noise comes from
+    ``sp_rng_uniform_pm1`` with (``seed``, call), the call counter advancing by one per batch as in ``BatchElasticDeform``; it and the
+    three filter passes are skipped for a batch in which no sample deforms.  A run is reproducible from ``seed`` alone."""
+
+    def __init__(self, rotate_deg=15.0, scale=(0.85, 1.15), alpha=100, sigma=4, gain=(0.9, 1.1), bias=(-0.1, 0.1),
+                 p_affine=0.5, p_elastic=0.5, p_intensity=0.5, label_threshold=0.5, seed=None):
+        for name, pair in (("scale", scale), ("gain", gain), ("bias", bias)):
+            if len(pair) != 2 or not pair[0] <= pair[1]:
+                raise ValueError("PatchAugment: %s is a (low, high) pair, got %r" % (name, pair))
+        if not scale[0] > 0:
+            raise ValueError("PatchAugment: scale must be positive, got %r" % (scale,))
+        for name, p in (("p_affine", p_affine), ("p_elastic", p_elastic), ("p_intensity", p_intensity)):
+            if not 0 <= p <= 1:
+                raise ValueError("PatchAugment: %s is a probability, got %r" % (name, p))
+        self.rotate_deg, self.scale, self.alpha, self.sigma, self.gain, self.bias = float(rotate_deg), tuple(scale), alpha, sigma, tuple(gain), tuple(bias)
+        self.p_affine, self.p_elastic, self.p_intensity = p_affine, p_elastic, p_intensity
+        self.label_threshold = label_threshold
+        if seed is None:
+            seed = datetime.datetime.now().second + datetime.datetime.now().microsecond
+        self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._rs = np.random.RandomState(self._seed & 0xFFFFFFFF)
+        self._calls = 0
+
+    @property
+    def thresh1(self):
+        """the ``thresh1`` argument of ``sp_patch_sample_batch``"""
+        return -1.0 if self.label_threshold is None else float(self.label_threshold)
+
+    def draw(self, B, C0):
+        """The host draws of one batch: ``xform`` (B, 16) fp32 (M[9], t[3], alpha_xy, alpha_z, two reserved words), ``intensity``
+        (B, C0, 2) fp32 (gain, bias) or ``None`` when no sample changes intensity (or there are no image channels), ``elastic``
+        (B,) bool, ``call``: the noise call counter of this batch."""
+        rs = self._rs
+        toss = rs.rand(B, 3)
+        angle = np.deg2rad(rs.uniform(-self.rotate_deg, self.rotate_deg, B))
+        s = rs.uniform(self.scale[0], self.scale[1], B)
+        gain = rs.uniform(self.gain[0], self.gain[1], (B, max(C0, 1)))
+        bias = rs.uniform(self.bias[0], self.bias[1], (B, max(C0, 1)))
+        affine, elastic, inten = toss[:, 0] < self.p_affine, toss[:, 1] < self.p_elastic, toss[:, 2] < self.p_intensity
+        xform = np.zeros((B, 16), dtype=np.float32)
+        xform[:, 0] = xform[:, 4] = xform[:, 8] = 1.0
+        for b in np.nonzero(affine)[0]:
+            c, sn = np.cos(angle[b]) / s[b], np.sin(angle[b]) / s[b]
+            xform[b, 0:2] = (c, -sn)
+            xform[b, 3:5] = (sn, c)
+        xform[elastic, 12] = float(self.alpha)
+        xform[elastic, 13] = float(self.alpha) * 0.22
+        intensity = None
+        if C0 > 0 and inten.any():
+            intensity = np.empty((B, C0, 2), dtype=np.float32)
+            intensity[:, :, 0] = np.where(inten[:, None], gain[:, :C0], 1.0)
+            intensity[:, :, 1] = np.where(inten[:, None], bias[:, :C0], 0.0)
+        call = self._calls
+        self._calls += 1
+        return {"xform": xform, "intensity": intensity, "elastic": elastic, "call": call}
+
+    def make_fields(self, draws, B, grid_zyx, device):
+        """(B, 3, d0, h0, w0) filtered noise on the image patch's grid (two launch groups: rng, three filter passes), or ``None``
+        when no sample of the batch deforms."""
+        if not draws["elastic"].any():
+            return None
+        from stroke_prediction_amd.runtime import lib as L, ops as O
+        d0, h0, w0 = grid_zyx
+        noise = torch.empty((B, 3, d0, h0, w0), dtype=torch.float32, device=device)
+        as_i64 = lambda u: u - (1 << 64) if u >= (1 << 63) else u
+        L.call("sp_rng_uniform_pm1", O.ptr(noise), B * 3, d0 * h0 * w0, as_i64(self._seed), as_i64(draws["call"] & 0xFFFFFFFFFFFFFFFF),
+               O.stream())
+        fields, tmp = torch.empty_like(noise), torch.empty_like(noise)
+        L.call("sp_gaussian_filter3d_batch", O.ptr(noise), O.ptr(fields), O.ptr(tmp), B * 3, d0, h0, w0, float(self.sigma), 4.0, O.stream())
+        return fields
+
+
+def _sample_launch(cache, table, ext0, pad0, padval0, ext1, pad1, augment):
+    """``_gather_launch`` through ``augment``: one pinned upload carries the table, ``xform`` and ``intensity`` (int32 and fp32 words
+    of one buffer), ``sp_patch_sample_batch`` builds the batch; the noise and filter launches come first when a sample deforms."""
+    import ctypes
+    from stroke_prediction_amd.runtime import lib as L, ops as O
+    src0, src1 = cache.images, cache.labels
+    _require_cuda(src0 if src0 is not None else src1, "CachedBatchLoader")
+    dev = (src0 if src0 is not None else src1).device
+    B = int(table.shape[0])
+    Z, Y, X = cache.shape_zyx
+    C0 = src0.shape[1] if src0 is not None else 0
+    draws = augment.draw(B, C0)
+    inten = draws["intensity"]
+    host = torch.empty(B * 21 + (B * C0 * 2 if inten is not None else 0), dtype=torch.int32)
+    host[:B * 5] = table.reshape(-1)
+    host[B * 5:B * 21].view(torch.float32).copy_(torch.from_numpy(draws["xform"]).reshape(-1))
+    if inten is not None:
+        host[B * 21:].view(torch.float32).copy_(torch.from_numpy(inten).reshape(-1))
+    words = host.pin_memory().to(dev, non_blocking=True)
+    table_dev = words[:B * 5].view(B, 5)
+    xform_dev = words[B * 5:B * 21].view(torch.float32)
+    inten_dev = words[B * 21:].view(torch.float32) if inten is not None else None
+    fields = augment.make_fields(draws, B, (ext0[2], ext0[1], ext0[0]), dev)
+    dst0 = torch.empty((B, C0, ext0[2], ext0[1], ext0[0]), dtype=torch.float32, device=dev) if src0 is not None else None
+    dst1 = torch.empty((B, src1.shape[1], ext1[2], ext1[1], ext1[0]), dtype=torch.float32, device=dev) if src1 is not None else None
+    i3 = lambda v: (ctypes.c_int32 * 3)(*[int(a) for a in v])
+    L.call("sp_patch_sample_batch", O.ptr(src0), O.ptr(dst0), C0, i3(ext0), i3(pad0), float(padval0),
+           O.ptr(src1), O.ptr(dst1), src1.shape[1] if src1 is not None else 0, i3(ext1), i3(pad1), augment.thresh1, O.ptr(table_dev),
+           O.ptr(xform_dev), O.ptr(fields) if fields is not None else None, O.ptr(inten_dev) if inten_dev is not None else None,
+           len(cache), B, Z, Y, X, O.stream())
+    return (dst0 if dst0 is not None else []), (dst1 if dst1 is not None else []), table_dev
+
+
 _CHAIN_ORDER = ("ResamplePlaneXY", "flip", "PadImages", "RandomPatch", "ToTensor")
 
 
@@ -651,18 +772,20 @@ class CachedBatchLoader(object):
     """The loader of ``_loader`` over a ``DeviceCaseCache``: the same index order (``SubsetRandomSampler`` + ``BatchSampler``,
     ``drop_last=False``), the same batch dict (keys, dtypes, shapes, devices) as the collated batch of the per-sample chain
     ``transforms``, built per batch by one pinned upload of the (B, 5) table, one ``sp_patch_gather_batch`` launch and one
-    ``index_select`` for ``clinical``; ``batch_transform`` is applied afterwards.  Random draws come from Python's ``random``, per
+    ``index_select`` for ``clinical``; ``batch_transform`` is applied afterwards.  With ``patch_augment`` (a ``PatchAugment``) the launch
+    is ``sp_patch_sample_batch`` and the upload also carries its transforms; the batch dict is the same.  Random draws come from Python's ``random``, per
     sample in the chain's order (``random.random()`` of ``HemisphericFlip``, then ``randint`` for x, y, z of ``RandomPatch``): with
     equal ``random`` state a batch equals the per-sample chain on the same cases bit for bit.  ``ResamplePlaneXY`` was applied
     when the cache was filled.  ``last_table``: the host copy of the latest batch's table."""
 
-    def __init__(self, cache, items, batch_size, transforms, batch_transform=None):
+    def __init__(self, cache, items, batch_size, transforms, batch_transform=None, patch_augment=None):
         from torch.utils.data.sampler import BatchSampler, SubsetRandomSampler
         self._stages = _parse_chain(transforms)
         missing = [i for i in items if i not in cache.slot_of]
         if missing:
             raise ValueError("CachedBatchLoader: items %r are not in the cache" % (missing,))
         self.cache, self.dataset, self.batch_size, self.batch_transform = cache, cache.dataset, batch_size, batch_transform
+        self.patch_augment = patch_augment
         self.sampler = SubsetRandomSampler(items)
         self.batch_sampler = BatchSampler(self.sampler, batch_size, drop_last=False)
         self.last_table = None
@@ -702,7 +825,11 @@ class CachedBatchLoader(object):
         cache = self.cache
         table = torch.tensor([self._row(int(i)) for i in items], dtype=torch.int32)
         self.last_table = table
-        images, labels, table_dev = _gather_launch(cache, table, self._ext0, self._pad0, self._padval0, self._ext1, (0, 0, 0))
+        if self.patch_augment is not None:
+            images, labels, table_dev = _sample_launch(cache, table, self._ext0, self._pad0, self._padval0, self._ext1, (0, 0, 0),
+                                                       self.patch_augment)
+        else:
+            images, labels, table_dev = _gather_launch(cache, table, self._ext0, self._pad0, self._padval0, self._ext1, (0, 0, 0))
         slots = table[:, 0].tolist()
         batch = {KEY_CASE_ID: default_collate([cache.case_ids[s] for s in slots]),
                  KEY_CLINICAL_IDX: default_collate([cache.clinical_idx[s] for s in slots]),
@@ -720,56 +847,68 @@ def _cache_prefix(chains):
     return [found[0]] if found[0] is not None else []
 
 
-def _cached_loaders(modalities, labels, chains, item_lists, batch_size, batch_transforms):
+def _cached_loaders(modalities, labels, chains, item_lists, batch_size, batch_transforms, patch_augments=None):
     if not torch.cuda.is_available():
         raise RuntimeError("device_cache=True (stroke_prediction_amd) needs a GPU: the case cache lives in device memory and the "
                            "batches are gathered by a HIP kernel; there is no CPU path")
     ds = _dataset(modalities, labels, _cache_prefix(chains), "cuda")
     cache = DeviceCaseCache(ds, "cuda", items=[i for items in item_lists for i in items])
-    return [CachedBatchLoader(cache, items, batch_size, chain, bt) for chain, items, bt in zip(chains, item_lists, batch_transforms)]
+    patch_augments = patch_augments or [None] * len(chains)
+    return [CachedBatchLoader(cache, items, batch_size, chain, bt, pa)
+            for chain, items, bt, pa in zip(chains, item_lists, batch_transforms, patch_augments)]
+
+
+def _check_patch_augment(patch_augment, device_cache):
+    if patch_augment is not None and not device_cache:
+        raise ValueError("patch_augment needs device_cache=True: the patches are sampled from the device-resident case cache "
+                         "(sp_patch_sample_batch); the per-sample chain has no such path")
 
 
 def split_data_loader3D(modalities, labels, indices, batch_size, random_seed=None, valid_size=0.5, shuffle=True,
                         num_workers=4, pin_memory=False, train_transform=[], valid_transform=[], batch_transform=None,
-                        device_cache=False):
+                        device_cache=False, patch_augment=None):
     """data.py:113-147: one fold -> (training loader, validation loader); the first ``valid_size`` share of the
     (seed-shuffled) fold validates.  ``batch_transform`` (e.g. ``BatchElasticDeform``): applied to every collated TRAINING
     batch; the validation loader never gets it.  ``device_cache``: both loaders are ``CachedBatchLoader``s over one shared
-    ``DeviceCaseCache`` (needs a GPU)."""
+    ``DeviceCaseCache`` (needs a GPU).  ``patch_augment`` (a ``PatchAugment``; needs ``device_cache``): the TRAINING loader samples
+    its patches through it; the validation loader never gets it."""
     assert 0 <= valid_size <= 1, "[!] valid_size should be in the range [0, 1]."
     assert train_transform and valid_transform, "You must provide at least a numpy-to-torch transformation."
+    _check_patch_augment(patch_augment, device_cache)
     dev = _pipeline_device()
     ds_train, ds_valid = _dataset(modalities, labels, train_transform, dev), _dataset(modalities, labels, valid_transform, dev)
     items = _fold_items(ds_train, indices, shuffle, random_seed)
     split = int(np.floor(valid_size * len(items)))
     if device_cache:
         return tuple(_cached_loaders(modalities, labels, [train_transform, valid_transform], [items[split:], items[:split]], batch_size,
-                                     [batch_transform, None]))
+                                     [batch_transform, None], [patch_augment, None]))
     return (_loader(ds_train, items[split:], batch_size, num_workers, pin_memory, True, batch_transform),
             _loader(ds_valid, items[:split], batch_size, num_workers, pin_memory, False))
 
 
 def single_data_loader3D(modalities, labels, indices, batch_size, random_seed=None, valid_size=0.5, shuffle=True,
-                         num_workers=4, pin_memory=False, train_transform=[], batch_transform=None, device_cache=False):
-    """data.py:150-172; ``batch_transform``, ``device_cache``: as for ``split_data_loader3D``."""
+                         num_workers=4, pin_memory=False, train_transform=[], batch_transform=None, device_cache=False,
+                         patch_augment=None):
+    """data.py:150-172; ``batch_transform``, ``device_cache``, ``patch_augment``: as for ``split_data_loader3D``."""
     assert train_transform, "You must provide at least a numpy-to-torch transformation."
+    _check_patch_augment(patch_augment, device_cache)
     ds = _dataset(modalities, labels, train_transform, _pipeline_device())
     items = _fold_items(ds, indices, shuffle, random_seed)
     if device_cache:
-        return _cached_loaders(modalities, labels, [train_transform], [items], batch_size, [batch_transform])[0]
+        return _cached_loaders(modalities, labels, [train_transform], [items], batch_size, [batch_transform], [patch_augment])[0]
     return _loader(ds, items, batch_size, num_workers, pin_memory, True, batch_transform)
 
 
 def get_stroke_shape_training_data(modalities, labels, train_transform, valid_transform, fold_indices, ratio, seed=4,
-                                   batchsize=2, split=True, batch_transform=None, device_cache=False):
+                                   batchsize=2, split=True, batch_transform=None, device_cache=False, patch_augment=None):
     """data.py:175-182 (``num_workers=0``: the transforms run in the training process -- here on its GPU)."""
     if split:
         return split_data_loader3D(modalities, labels, fold_indices, batchsize, random_seed=seed, valid_size=ratio,
                                    train_transform=train_transform, valid_transform=valid_transform, num_workers=0,
-                                   batch_transform=batch_transform, device_cache=device_cache)
+                                   batch_transform=batch_transform, device_cache=device_cache, patch_augment=patch_augment)
     return single_data_loader3D(modalities, labels, fold_indices, batchsize, random_seed=seed, valid_size=ratio,
                                 train_transform=train_transform, num_workers=0, batch_transform=batch_transform,
-                                device_cache=device_cache), None
+                                device_cache=device_cache, patch_augment=patch_augment), None
 
 
 get_stroke_prediction_training_data = get_stroke_shape_training_data      # data.py:185-192: the same factory

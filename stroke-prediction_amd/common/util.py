@@ -52,6 +52,9 @@ _UNET = [
     # the reference's script reads args.inbasepath and a batch size it hard-codes (train_unet_segmentation.py:12,57): made flags
     ("--inbasepath", dict(type=str, default=None, help="(MI355X build) path and filename base of a training to continue")),
     ("--batchsize", dict(type=int, default=6, help="(MI355X build) batch size (train_unet_segmentation.py:12 hard-codes 6)")),
+    ("--patchaugment", dict(action="store_true", default=False,
+                            help="(MI355X build) with --devicecache: rotate / scale / elastically deform the training patches and change "
+                                 "their intensity inside the kernel that builds the batch (data.PatchAugment, seeded by --seed)")),
 ]
 _SDM = [
     ("unet", dict(type=str, help="Path to model of Segmentation Unet")),
@@ -92,7 +95,16 @@ class CAEParser(ExpParser):
 
 
 class UnetParser(ExpParser):
+    """``--patchaugment`` samples the training patches from the device-resident case cache through a per-sample transform: it
+    goes with ``--devicecache`` (the per-sample chain has no such path)."""
     EXTRA = _UNET
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.patchaugment and not ns.devicecache:
+            self.error("--patchaugment needs --devicecache: the augmented patches are sampled from the device-resident case cache "
+                       "(sp_patch_sample_batch); the per-sample chain has no such path")
+        return ns
 
 
 class SDMParser(ExpParser):

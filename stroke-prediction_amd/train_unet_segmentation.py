@@ -32,8 +32,10 @@ def build_loaders(args):
     chain = lambda: [data.ResamplePlaneXY(args.xyresample), data.HemisphericFlipFixedToCaseId(split_id=args.hemisflipid),
                      data.PadImages(pad[0], pad[1], pad[2], pad_value=0), data.RandomPatch(*PATCH, pad[0], pad[1], pad[2]),
                      data.ToTensor()]
+    augment = data.PatchAugment(seed=args.seed) if args.patchaugment else None
     loaders = data.get_stroke_shape_training_data(IMAGE_VOLUMES, LABEL_VOLUMES, chain(), chain(), args.fold, args.validsetsize,
-                                                  seed=args.seed, batchsize=args.batchsize, device_cache=args.devicecache)
+                                                  seed=args.seed, batchsize=args.batchsize, device_cache=args.devicecache,
+                                                  patch_augment=augment)
     print('Size training set:', len(loaders[0].sampler.indices), 'samples | Size validation set:', len(loaders[1].sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
     return loaders
