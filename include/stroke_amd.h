@@ -43,6 +43,8 @@ enum { SP_REDUCE_ROWS = 8 };
  * its accumulator sums[SP_REDUCE_ROWS][SP_VLOSS_PITCH(C)], four columns per channel */
 enum { SP_VLOSS_DICE = 1, SP_VLOSS_BCE = 2 };
 #define SP_VLOSS_PITCH(C) ((4 * (C) + 15) / 16 * 16)
+/* the boundary-loss family (sp_bloss_*): the same four columns per channel, the fourth holding sum o*phi */
+#define SP_BLOSS_PITCH(C) SP_VLOSS_PITCH(C)
 enum { SP_BF16 = 0, SP_F32 = 1,
        /* bf16 PAIR: value = hi + lo with hi = bf16(value) and lo = bf16(value - hi), stored as TWO bf16 tensors of the same
         * shape (the hi tensor is what the bf16 kernels of the backward pass read; the lo tensor lies lo_delta bytes behind it).
@@ -816,6 +818,37 @@ int sp_cae_loss_crit_bwd(const float* c, int64_t cbs, const float* p, int64_t pb
                          const float* tc, int64_t tcbs, const float* tp, int64_t tpbs, const float* tl, int64_t tlbs, int32_t B, int64_t DHW,
                          const float* coef, const float* up, float* dc, float* dp, float* dl, float* di, const float* zi, const float* zl,
                          int64_t nlat, float* dzi, float* dzl, sp_stream_t stream);
+
+/* ------------------------------------------------------------------ boundary (signed-distance) criteria: the boundary loss of
+ * Kervadec et al., "Boundary loss for highly unbalanced segmentation" (MIDL 2019), mean(o * phi(t)), alone or beside Dice.
+ * sp_signed_distance_batch: t as for sp_dice_sums ((B, C, D*H*W) fp32, contiguous per sample, batch stride in elements); phi: dense
+ * (B, C, D, H, W) fp32.  Per volume (b, c), with M = t > 0.5 and unit spacing: outside M the Euclidean distance to the nearest voxel
+ * of M, inside M -(distance to the nearest voxel outside M - 1), and phi = 0 everywhere when M is empty or full (the one_hot2dist
+ * of the paper's code; scipy: edt(~M) * ~M - (edt(M) - 1) * M).  The inside and the outside transform of all B * C volumes are one
+ * (2 B C D, H, W) stack scanned by the axis scan of the surface distances: one seed launch, one launch per axis of extent > 1, one
+ * launch that takes the roots -- whatever B and C.  Squared distances are exact integers; the root and the - 1 are taken in fp64
+ * and rounded once.  Empty / full is decided on the device from exact integer counts (one partial per seed workgroup, written, not
+ * added): no host read, no allocation -- the call can be captured.  ws: sp_signed_distance_batch_workspace floats (4 B C D H W for
+ * the two ping-pong stacks + 64 B C for the counts).  Extents below 4096 each (the axis scan's exact range), B * C <= 65535. */
+int sp_signed_distance_batch_workspace(int32_t B, int32_t C, int32_t D, int32_t H, int32_t W, int64_t* floats);
+int sp_signed_distance_batch(const float* t, int64_t t_bstride, int32_t B, int32_t C, int32_t D, int32_t H, int32_t W, float* phi,
+                             float* ws, int64_t ws_floats, sp_stream_t stream);
+/* The sp_vloss_* triple with one more input, phi (dense (B, C, DHW), e.g. from sp_signed_distance_batch), and the moment sum o*phi in
+ * place of the BCE sum: sums[row][4*c + k] (fp64, zeroed by the caller; SP_REDUCE_ROWS replica rows of SP_BLOSS_PITCH(C) doubles) +=
+ * (sum o*t, sum o*o, sum t*t, sum o*phi) over batch and volume; dice == 0: only the fourth.  Reduction order and load widths as
+ * sp_vloss_sums (16-byte loads need phi + its rows aligned too). */
+int sp_bloss_sums(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* phi, int32_t B, int32_t C,
+                  int64_t DHW, int32_t dice, double* sums, sp_stream_t stream);
+/* loss = [w_dice ? 1 - sum_c wd_c (2 I_c + eps)/(O_c + T_c + eps) : 0] + sum_c wb_c * *scale * P_c / count; w_dice ([C], device) may
+ * be NULL = no Dice term; w_boundary ([C]) and scale (one float) are read from device memory, so that the boundary weight can
+ * change between replays of a captured graph.  count as for sp_vloss_finalize_clear.  coef[3c .. 3c+2] = (ca, cb, cd):
+ * d loss / d o = ca*t + cb*o + cd*phi, cd = wb_c * *scale / count.  The replica rows are zeroed again after they are read. */
+int sp_bloss_finalize_clear(double* sums, const float* w_dice, const float* w_boundary, const float* scale, double eps, double count,
+                            int32_t C, float* loss, float* coef, sp_stream_t stream);
+/* dout (dense (B, C, DHW)) = *upstream * (ca[c]*t + cb[c]*o + cd[c]*phi); upstream: device pointer to the scalar gradient
+ * (NULL = 1).  No gradient goes to t or phi. */
+int sp_bloss_bwd(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* phi, const float* coef,
+                 const float* upstream, int32_t B, int32_t C, int64_t DHW, float* dout, sp_stream_t stream);
 
 /* ------------------------------------------------------------------ fused classify head (Unet3D.py:49-54,75-77)
  * seg = sigmoid(W2 * lrelu(W1*x + b1) + b2): x channels-last [B*nvox][CP], seg NCDHW fp32 [B][NC][nvox].

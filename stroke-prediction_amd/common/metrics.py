@@ -11,6 +11,11 @@ no host implementation here; the checker is ``oracle/measures.py``.
 ``BCELoss`` and ``DiceBCELoss`` -- the ``# nn.BCELoss()`` the reference's training scripts name beside their Dice criterion -- run on
 one kernel family of their own (``sp_vloss_sums`` / ``_finalize_clear`` / ``_bwd``), take the same fused routes as ``BatchDiceLoss``
 (``mean_of_channel_losses``, ``cae_reconstruction_loss``) and are picked by name with ``make_criterion``.
+
+``BoundaryLoss`` and ``DiceBoundaryLoss`` -- the boundary loss of Kervadec et al. (MIDL 2019), mean(o * phi(t)) with phi the signed
+Euclidean distance map of the label, alone or added to Dice with a weight that can grow over the epochs -- compute phi per sample
+and channel on the device (``sp_signed_distance_batch``) and run on ``sp_bloss_sums`` / ``_finalize_clear`` / ``_bwd``; they take the
+``mean_of_channel_losses`` route, and the CAE learners compose them literally.
 """
 import numpy
 import torch
@@ -236,6 +241,174 @@ class DiceBCELoss(LossModule):
                                   (float(self._bce_weight) / C,) * C, float(self._epsilon))
 
 
+_BLOSS_SUMS = {}     # (device, C, stream) -> [replica rows of the boundary-loss sums (zero between calls), busy]
+
+
+def signed_distance_workspace_floats(B, C, D, H, W):
+    """floats of workspace ``sp_signed_distance_batch`` needs: 4 B C D H W + 64 B C"""
+    import ctypes as CT
+    from stroke_prediction_amd.runtime import lib as L
+    n = CT.c_int64(0)
+    L.call("sp_signed_distance_batch_workspace", int(B), int(C), int(D), int(H), int(W), CT.byref(n))
+    return int(n.value)
+
+
+def signed_distance_batch(targets):
+    """phi (B, C, D, H, W) fp32 of a (B, C, D, H, W) GPU label tensor (channel-slice views are read in place): per volume the signed
+    Euclidean distance map of ``targets > 0.5`` -- positive outside, -(distance - 1) inside, zero for an empty or a full mask.  Five
+    launches at most whatever B and C, no host read; the map and the workspace come from torch's allocator (the graph pool under
+    capture)."""
+    from stroke_prediction_amd.runtime import lib as L, ops as O
+    if not targets.is_cuda or targets.dim() != 5:
+        raise RuntimeError("signed_distance_batch (stroke_prediction_amd) runs on the GPU on (B, C, D, H, W) tensors")
+    t, tbs = _batch_strided(targets)
+    B, C, D, H, W = t.shape
+    phi = torch.empty((B, C, D, H, W), dtype=torch.float32, device=t.device)
+    nws = signed_distance_workspace_floats(B, C, D, H, W)
+    ws = torch.empty(nws, dtype=torch.float32, device=t.device)
+    L.call("sp_signed_distance_batch", O.ptr(t), tbs, B, C, D, H, W, O.ptr(phi), O.ptr(ws), nws, O.stream())
+    return phi
+
+
+class _BoundaryLossFn(torch.autograd.Function):
+    """loss = [1 - sum_c wd_c (2 I_c + eps) / (O_c + T_c + eps)] + sum_c wb_c * scale * mean_c(o * phi), the Dice bracket absent when
+    its weights are None; phi = signed_distance_batch(targets), scale a one-float device tensor read by the finalize kernel (a
+    captured step follows its schedule).  Shaped like _VoxelLossFn: the signed-distance launches, sums and finalize forward, one
+    launch backward.  In the exact data-parallel mode the sums are all-reduced and the element count is the global one; phi is
+    local."""
+
+    @staticmethod
+    def forward(ctx, outputs, targets, w_dice, w_boundary, scale, eps):
+        from stroke_prediction_amd.runtime import lib as L, ops as O
+        from stroke_prediction_amd.runtime.layers import SYNC, _allreduce
+        o, obs = _batch_strided(outputs)
+        t, tbs = _batch_strided(targets)
+        B, C = o.shape[0], o.shape[1]
+        dhw = o.numel() // (B * C)
+        phi = signed_distance_batch(t)
+        # one accumulator per (device, C, stream), left zero by sp_bloss_finalize_clear; ``busy`` as in _DiceFn
+        key = (o.device, C, int(torch.cuda.current_stream(o.device).cuda_stream))
+        ent = _BLOSS_SUMS.get(key)
+        if ent is None or ent[1]:
+            ent = _BLOSS_SUMS[key] = [torch.zeros(L.SP_REDUCE_ROWS, L.SP_BLOSS_PITCH(C), dtype=torch.float64, device=o.device), False]
+        sums = ent[0]
+        ent[1] = True
+        L.call("sp_bloss_sums", O.ptr(o), obs, O.ptr(t), tbs, O.ptr(phi), B, C, dhw, 0 if w_dice is None else 1, O.ptr(sums), O.stream())
+        count = float(B * dhw)
+        if SYNC["on"]:                  # whole-batch sums and a whole-batch mean
+            _allreduce(sums)
+            count *= SYNC["world"]
+        wd = None if w_dice is None else _weights_on(o.device, w_dice)      # cached: no host->device copy inside a captured step
+        wb = _weights_on(o.device, w_boundary)
+        loss = torch.empty((), dtype=torch.float32, device=o.device)
+        coef = torch.empty(3 * C, dtype=torch.float32, device=o.device)
+        L.call("sp_bloss_finalize_clear", O.ptr(sums), None if wd is None else O.ptr(wd), O.ptr(wb), O.ptr(scale), float(eps), count, C,
+               O.ptr(loss), O.ptr(coef), O.stream())
+        ent[1] = False
+        ctx.save_for_backward(o, t, phi, coef)
+        ctx.strides = (obs, tbs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        from stroke_prediction_amd.runtime import lib as L, ops as O
+        o, t, phi, coef = ctx.saved_tensors
+        obs, tbs = ctx.strides
+        B, C = o.shape[0], o.shape[1]
+        up = gloss if (gloss.dtype == torch.float32 and gloss.is_contiguous()) else gloss.float().contiguous()
+        d = torch.empty(o.shape, dtype=torch.float32, device=o.device)
+        L.call("sp_bloss_bwd", O.ptr(o), obs, O.ptr(t), tbs, O.ptr(phi), O.ptr(coef), O.ptr(up), B, C, o.numel() // (B * C), O.ptr(d),
+               O.stream())
+        return d, None, None, None, None, None
+
+
+class _ScheduledBoundaryWeight(object):
+    """The boundary term's scalar: a Python value and its copy in a persistent one-float device tensor (made on first use, per device)
+    that the finalize kernel reads.  ``set_boundary_weight`` / ``adapt`` run between steps; a captured step is not re-captured."""
+
+    def _init_schedule(self, weight, ramp=0.0):
+        self._boundary_weight0 = float(weight)
+        self._boundary_ramp = float(ramp)
+        self._boundary_weight = float(weight)
+        self._scale_dev = {}
+
+    def boundary_weight(self):
+        return self._boundary_weight
+
+    def set_boundary_weight(self, w):
+        """host value and every device copy (one host -> device copy each); call it outside the step"""
+        self._boundary_weight = float(w)
+        for dev_scale in self._scale_dev.values():
+            dev_scale.copy_(torch.tensor([self._boundary_weight], dtype=torch.float32))
+
+    def set_boundary_schedule(self, weight, ramp=0.0):
+        """weight at epoch 0 and its growth per epoch (``adapt``)"""
+        self._boundary_weight0 = float(weight)
+        self._boundary_ramp = float(ramp)
+        self.set_boundary_weight(weight)
+
+    def adapt(self, epoch):
+        """min(1.0, w0 + ramp * epoch): the rebalancing schedule of the paper (ramp 0.01); Learner.adapt_criterion calls it"""
+        self.set_boundary_weight(min(1.0, self._boundary_weight0 + self._boundary_ramp * epoch))
+
+    def _scale_on(self, device):
+        key = str(device)
+        if key not in self._scale_dev:
+            self._scale_dev[key] = torch.tensor([self._boundary_weight], dtype=torch.float32, device=device)
+        return self._scale_dev[key]
+
+
+class BoundaryLoss(LossModule, _ScheduledBoundaryWeight):
+    """``weight * sum_c w_c mean_c(o * phi_c(t))`` on (B, C, D, H, W) GPU tensors (channel dim 1), phi the signed distance map of
+    ``t > 0.5`` per sample and channel (``signed_distance_batch``).  The default channel weights, 1 / C each, are the mean over
+    everything.  No gradient goes to the targets."""
+
+    def __init__(self, label_weights=None, weight=1.0):
+        super(BoundaryLoss, self).__init__()
+        self._label_weights = label_weights
+        self._dim = 1
+        self._init_schedule(weight)
+
+    def weights(self, C):
+        if self._label_weights is None:
+            return (1.0 / C,) * C
+        return tuple(float(w) for w in self._label_weights)
+
+    def forward(self, outputs, targets):
+        _check_voxel_loss_inputs("BoundaryLoss", outputs, targets, self._label_weights)
+        return _BoundaryLossFn.apply(outputs, targets, None, self.weights(outputs.shape[1]), self._scale_on(outputs.device), 0.0)
+
+
+class DiceBoundaryLoss(LossModule, _ScheduledBoundaryWeight):
+    """``BatchDiceLoss(label_weights, epsilon)(o, t) + boundary_weight * BoundaryLoss()(o, t)`` in one signed-distance set and one
+    sums / finalize / backward set; ``adapt(epoch)`` moves boundary_weight along its ramp."""
+
+    def __init__(self, label_weights, boundary_weight=0.01, epsilon=0.0000001):
+        super(DiceBoundaryLoss, self).__init__()
+        self._label_weights = label_weights
+        self._epsilon = epsilon
+        self._dim = 1
+        self._init_schedule(boundary_weight)
+
+    def forward(self, outputs, targets):
+        _check_voxel_loss_inputs("DiceBoundaryLoss", outputs, targets, self._label_weights)
+        C = outputs.shape[1]
+        return _BoundaryLossFn.apply(outputs, targets, tuple(float(w) for w in self._label_weights), (1.0 / C,) * C,
+                                     self._scale_on(outputs.device), float(self._epsilon))
+
+
+def _single_label_boundary_terms(criterion):
+    """(Dice weight or None, boundary channel weight, eps) of a BoundaryLoss / DiceBoundaryLoss that weighs ONE label class -- what
+    ``mean_of_channel_losses`` evaluates per channel --, or None for anything else."""
+    if getattr(criterion, "_dim", None) != 1:
+        return None
+    if isinstance(criterion, BoundaryLoss) and (criterion._label_weights is None or len(criterion._label_weights) == 1):
+        return None, criterion.weights(1)[0], 0.0
+    if isinstance(criterion, DiceBoundaryLoss) and len(criterion._label_weights) == 1:
+        return float(criterion._label_weights[0]), 1.0, float(criterion._epsilon)
+    return None
+
+
 def _single_label_terms(criterion):
     """(Dice weight or None, BCE weight or None, eps) of a criterion that weighs ONE label class -- what the fused routes below
     evaluate per channel / per reconstruction --, or None for anything else."""
@@ -251,14 +424,27 @@ def _single_label_terms(criterion):
 
 
 def make_criterion(name):
-    """The training scripts' ``--criterion``: ``dice`` (the reference's choice), ``bce`` (the one its comment names), ``dicebce``."""
+    """The training scripts' ``--criterion``: ``dice`` (the reference's choice), ``bce`` (the one its comment names), ``dicebce``,
+    ``boundary`` (the signed-distance loss) and ``diceboundary`` (Dice + boundary weight * boundary loss)."""
     if name == "dice":
         return BatchDiceLoss([1.0])
     if name == "bce":
         return BCELoss()
     if name == "dicebce":
         return DiceBCELoss([1.0])
-    raise ValueError("criterion %r: one of dice, bce, dicebce" % (name,))
+    if name == "boundary":
+        return BoundaryLoss()
+    if name == "diceboundary":
+        return DiceBoundaryLoss([1.0])
+    raise ValueError("criterion %r: one of dice, bce, dicebce, boundary, diceboundary" % (name,))
+
+
+def configure_criterion(criterion, args):
+    """Apply the training scripts' ``--boundaryweight`` / ``--boundaryramp`` to a criterion that has a boundary term; any other
+    criterion is returned as it is."""
+    if isinstance(criterion, (BoundaryLoss, DiceBoundaryLoss)):
+        criterion.set_boundary_schedule(getattr(args, "boundaryweight", criterion.boundary_weight()), getattr(args, "boundaryramp", 0.0))
+    return criterion
 
 
 class _CaeLossFn(torch.autograd.Function):
@@ -355,8 +541,17 @@ def mean_of_channel_losses(criterion, outputs, targets):
     produce), this is BatchDiceLoss over n channels with weights w/n: evaluated in one sums / finalize / backward
     launch on the base tensors, and the gradient lands on the segmentation directly (no slice-backward zero-fill,
     copy and add per channel).  A single-label BCELoss (weights 1/n) or DiceBCELoss (Dice weights w/n, BCE weights
-    bce_weight/n) takes the same route on the sp_vloss_* kernels.  Anything else: the literal sum of calls."""
+    bce_weight/n) takes the same route on the sp_vloss_* kernels, a single-label BoundaryLoss / DiceBoundaryLoss on
+    sp_signed_distance_batch and the sp_bloss_* kernels (one signed-distance set for all n channels).  Anything else: the literal
+    sum of calls."""
     n = len(outputs)
+    bterms = _single_label_boundary_terms(criterion)
+    if bterms is not None and n > 1 and outputs[0].is_cuda and outputs[0].dim() == 5:
+        ob, tb = _stacked_base(outputs), _stacked_base(targets)
+        if ob is not None and tb is not None:
+            w_dice, w_bnd, eps = bterms
+            return _BoundaryLossFn.apply(ob, tb, None if w_dice is None else (w_dice / n,) * n, (w_bnd / n,) * n,
+                                         criterion._scale_on(ob.device), eps)
     terms = _single_label_terms(criterion)
     if terms is not None and n > 1 and outputs[0].is_cuda:
         ob, tb = _stacked_base(outputs), _stacked_base(targets)

@@ -31,9 +31,15 @@ _EXPERIMENT = [
     ("--devicecache", dict(action="store_true", default=False,
                            help="(MI355X build) upload every case once and gather each batch from the device-resident cache with one "
                                 "kernel launch (data.DeviceCaseCache / CachedBatchLoader)")),
-    ("--criterion", dict(type=str, default="dice", choices=["dice", "bce", "dicebce"],
+    ("--criterion", dict(type=str, default="dice", choices=["dice", "bce", "dicebce", "boundary", "diceboundary"],
                          help="(MI355X build) training criterion (metrics.make_criterion): BatchDiceLoss([1.0]) as the reference, the "
-                              "nn.BCELoss() its scripts name as the alternative, or their sum")),
+                              "nn.BCELoss() its scripts name as the alternative, their sum, the boundary (signed-distance) loss "
+                              "mean(o * phi(t)), or Dice + boundary weight * boundary loss")),
+    ("--boundaryweight", dict(type=float, default=0.01,
+                              help="(MI355X build) --criterion boundary / diceboundary: weight of the boundary term at epoch 0")),
+    ("--boundaryramp", dict(type=float, default=0.0,
+                            help="(MI355X build) --criterion boundary / diceboundary: the weight grows by this much per epoch, capped at "
+                                 "1.0 (Kervadec et al. use 0.01)")),
 ]
 _CAE = [
     ("--epochs", dict(type=int, default=300, help="Number of epochs")),

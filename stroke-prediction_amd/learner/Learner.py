@@ -1,7 +1,7 @@
 """Template-method training loop (API of the reference ``learner/Learner.py:16-226``).
 
 Hooks kept by name: ``inference_step``, ``loss_step``, ``batch_metrics_step``, ``train_batch``,
-``validate_batch``, ``adapt_lr``, ``adapt_betas``, ``print_epoch``, ``plot_epoch``, ``visualize_epoch``,
+``validate_batch``, ``adapt_lr``, ``adapt_betas``, ``adapt_criterion``, ``print_epoch``, ``plot_epoch``, ``visualize_epoch``,
 ``run_training``, ``path``, ``save_model`` / ``load_model``, ``save_training`` / ``load_training``.
 The three lines that matter for speed -- ``zero_grad`` / ``backward`` / ``step`` (Learner.py:120-122) -- drive
 the HIP path: backward is the model's fused autograd node, the step is ``FusedAdam`` when the caller
@@ -159,6 +159,13 @@ class Learner(Inference):
 
     def adapt_betas(self, epoch):
         pass
+
+    def adapt_criterion(self, epoch):
+        """a criterion with a schedule of its own (``metrics.BoundaryLoss`` / ``DiceBoundaryLoss``: the boundary weight's ramp) follows
+        the epoch; it writes a device scalar outside the step, so a captured step needs no recapture.  Others have no ``adapt``."""
+        adapt = getattr(getattr(self, '_criterion', None), 'adapt', None)
+        if adapt is not None:
+            adapt(epoch)
 
     # ------------------------------------------------------------------ checkpoints (Learner.py:90-114)
     def load_model(self, cuda=True):
@@ -371,6 +378,7 @@ class Learner(Inference):
         for epoch in range(self.get_start_epoch(), self._n_epochs):
             self.adapt_lr(epoch)
             self.adapt_betas(epoch)
+            self.adapt_criterion(epoch)
 
             self._model.train()
             metrics = self._run_phase(self._dataloader_training, self.train_batch, epoch)

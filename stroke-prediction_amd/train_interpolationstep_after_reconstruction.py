@@ -50,9 +50,11 @@ def train(args):
                                                              device_cache=args.devicecache)
     print('Size training set:', len(ds_train.sampler.indices), 'samples | Size validation set:', len(ds_valid.sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
+    criterion = metrics.make_criterion(args.criterion)
+    metrics.configure_criterion(criterion, args)      # --boundaryweight / --boundaryramp; nothing for the other criteria
     learner = CaeStepLearner(ds_train, ds_valid, cae, optimizer, scheduler, n_epochs=args.epochs,
                              path_previous_base=args.inbasepath, path_outputs_base=args.outbasepath,
-                             criterion=metrics.make_criterion(args.criterion), verbose=False)
+                             criterion=criterion, verbose=False)
     learner.run_training()
     return learner
 

@@ -73,9 +73,11 @@ def train(args):
     cae, enc = build_models(args)
     optimizer, scheduler = build_optimizer(args, cae, enc)
     ds_train, ds_valid = build_loaders(args)
+    criterion = metrics.make_criterion(args.criterion)
+    metrics.configure_criterion(criterion, args)      # --boundaryweight / --boundaryramp; nothing for the other criteria
     learner = CaePredictionLearner(ds_train, ds_valid, cae, enc, optimizer, scheduler, n_epochs=args.epochs,
                                    path_previous_base=args.inbasepath, path_outputs_base=args.outbasepath,
-                                   criterion=metrics.make_criterion(args.criterion))
+                                   criterion=criterion)
     learner.run_training()
     return learner
 

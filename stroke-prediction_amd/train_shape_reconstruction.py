@@ -69,9 +69,11 @@ def train(args):
     cae = build_model(args)
     optimizer, scheduler = build_optimizer(args, cae)
     ds_train, ds_valid = build_loaders(args)
+    criterion = metrics.make_criterion(args.criterion)
+    metrics.configure_criterion(criterion, args)      # --boundaryweight / --boundaryramp; nothing for the other criteria
     learner = CaeReconstructionLearner(ds_train, ds_valid, cae, optimizer, scheduler, n_epochs=args.epochs,
                                        path_previous_base=args.inbasepath, path_outputs_base=args.outbasepath,
-                                       criterion=metrics.make_criterion(args.criterion), normalization_hours_penumbra=args.normalize,
+                                       criterion=criterion, normalization_hours_penumbra=args.normalize,
                                        graph=args.graph)
     learner.run_training()
     return learner

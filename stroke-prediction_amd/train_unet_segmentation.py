@@ -53,7 +53,9 @@ def train(args):
         optimizer = torch.optim.Adam(params, **hyper)
     scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, args.lrsteps) if args.lrsteps else None
     ds_train, ds_valid = build_loaders(args)
-    learner = UnetSegmentationLearner(ds_train, ds_valid, unet, optimizer, scheduler, args.epochs, metrics.make_criterion(args.criterion),
+    criterion = metrics.make_criterion(args.criterion)
+    metrics.configure_criterion(criterion, args)      # --boundaryweight / --boundaryramp; nothing for the other criteria
+    learner = UnetSegmentationLearner(ds_train, ds_valid, unet, optimizer, scheduler, args.epochs, criterion,
                                       path_previous_base=args.inbasepath, path_outputs_base=args.outbasepath, graph=args.graph)
     learner.run_training()
     best = learner.path('save', learner.FNB_MODEL)
