@@ -999,6 +999,34 @@ int sp_patch_sample_batch(const float* src0, float* dst0, int32_t C0, const int3
                           const int32_t* table, const float* xform, const float* fields, const float* intensity,
                           int32_t N, int32_t B, int32_t Z, int32_t Y, int32_t X, sp_stream_t stream);
 
+/* Foreground-oversampled patch origins (common/data.py: ForegroundOversample; csrc/sp_fgpatch.hip).  labels (N, C1, Z, Y, X): the
+ * cache's label group.  Voxel (n, z, y, x) is FOREGROUND when labels[n, c, z, y, x] > threshold for some channel c whose bit is set
+ * in chanmask (bit c = channel c; C1 <= 32); a value equal to the threshold is not.  The foreground voxels of a case are numbered
+ * in the cache's C order (z, y, x): number k is numpy.flatnonzero(mask[n])[k].
+ * sp_fg_row_index -- once per (cache, chanmask, threshold), two launches: prefix (device, int32[N][Z Y + 1]) receives the exclusive
+ * prefix sum of the foreground counts of the x rows of each case, row r = z Y + y; prefix[n][Z Y] is the case's total.  One wave
+ * counts a row (lanes along x, a ballot per 64 voxels), one workgroup scans a case: integers, no atomics, the same result whatever
+ * the scheduling.  SP_EINVAL: a NULL pointer, a non-positive extent, C1 outside [1, 32], a chanmask that selects no channel below
+ * C1, 2^31 or more voxels per case or rows over all cases. */
+int sp_fg_row_index(const float* labels, int32_t N, int32_t C1, int32_t Z, int32_t Y, int32_t X, int32_t chanmask, float threshold,
+                    int32_t* prefix, sp_stream_t stream);
+/* Every batch, one launch, one 64-lane wave per sample: rewrites the origins of the gather's table (device, int32[B][5]: slot, ox,
+ * oy, oz, flip) IN PLACE so that the label patch holds a uniformly drawn foreground voxel of the sample's case.  draws (device,
+ * int32[B][5]): force, u, jx, jy, jz -- u the 32 bits of an unsigned word.  ext1 = {w1, h1, d1}, the label patch, and omax =
+ * padded - ext0, the largest legal origin (host arrays of three).  picked (device, int32[B][4], or NULL): (k, fx, fy, fz) per sample.
+ * A row is LEFT AS IT IS, and its picked is (-1, -1, -1, -1), when force == 0, when slot is outside [0, N), when the case's total
+ * prefix[slot][Z Y] is 0 (the origin already in the row is the fallback) and when the walk below does not find the voxel (labels
+ * written to after the index was built).  Otherwise k = ((uint64) u * total) >> 32; r = the row with prefix[r] <= k < prefix[r + 1]
+ * (bisection, at most 32 steps); the x row r is walked in chunks of 64 lanes (ballot, popcount; at most ceil(X / 64) chunks) to its
+ * voxel number k - prefix[r]: (fx, fy, fz) with r = fz Y + fy.  In the label frame f = (flip ? X - 1 - fx : fx, fy, fz); with j
+ * clamped to [0, ext1 - 1] the origin becomes o = clamp(f - j, 0, omax) per axis: group 1 of the gather reads source ox + x (pad1 =
+ * 0), so the voxel lands at label-patch position j when nothing clamps, and stays inside the label patch under either clamp when
+ * the patch's crop does not exceed the image padding.  One lane writes the three words.  SP_EINVAL: a NULL labels / prefix / draws /
+ * ext1 / omax / table, B < 1, what sp_fg_row_index rejects, ext1 < 1 or omax < 0 on an axis. */
+int sp_patch_origins_fg(const float* labels, const int32_t* prefix, int32_t N, int32_t C1, int32_t Z, int32_t Y, int32_t X,
+                        int32_t chanmask, float threshold, const int32_t* draws, const int32_t* ext1, const int32_t* omax,
+                        int32_t* table, int32_t* picked, int32_t B, sp_stream_t stream);
+
 /* ------------------------------------------------------------------ surface distances of the batch metrics
  * metrics.py:42-44 -> medpy 0.3.0 metric.binary.hd / assd (__surface_distances): border = mask XOR binary_erosion(mask)
  * with the cross structure of the array's rank (out-of-bounds = background), exact Euclidean distance transform of the

@@ -15,7 +15,8 @@ reproduces the reference's augmentation; ``ElasticDeform(device_noise=True)`` dr
 every case on the device (``DeviceCaseCache``) and builds each batch -- flip, padding, patch, layout, stack -- with one launch of
 ``sp_patch_gather_batch`` (csrc/sp_gather.hip; ``CachedBatchLoader``).  ``PatchAugment`` (``patch_augment=`` on the factories) makes
 that launch ``sp_patch_sample_batch`` (csrc/sp_sample.hip): rotation, scaling, elastic deformation and an intensity change per
-sample, images and labels through one field, in the kernel that builds the batch.
+sample, images and labels through one field, in the kernel that builds the batch.  ``ForegroundOversample`` (``foreground=``) forces
+a share of each cached batch onto lesion: ``sp_patch_origins_fg`` (csrc/sp_fgpatch.hip) rewrites those samples' origins on the device.
 """
 import datetime
 import random
@@ -588,18 +589,115 @@ class DeviceCaseCache(object):
         if self.images is not None and self.labels is not None and self.images.shape[2:] != self.labels.shape[2:]:
             raise ValueError("DeviceCaseCache: images %r and labels %r differ in extents" % (tuple(self.images.shape), tuple(self.labels.shape)))
         self.shape_zyx = tuple((self.images if self.images is not None else self.labels).shape[2:])
+        self._fg_index = {}
 
     def __len__(self):
         return len(self.items)
+
+    def foreground_index(self, channels=None, threshold=0.5):
+        """The row index of the cases' foreground voxels (``sp_fg_row_index``, csrc/sp_fgpatch.hip): int32 (N, Z * Y + 1) on the
+        device, the exclusive prefix sum of the per-x-row counts of the voxels whose label exceeds ``threshold`` in one of
+        ``channels`` (``None``: any label channel); the last column is the case's total.  Built on first use -- two launches, no host
+        read -- and kept per (channel mask, threshold); writing to ``labels`` afterwards makes it stale."""
+        if self.labels is None:
+            raise ValueError("DeviceCaseCache.foreground_index: the cache holds no labels")
+        from stroke_prediction_amd.runtime import lib as L, ops as O
+        C1 = int(self.labels.shape[1])
+        key = (_chanmask(channels, C1, "DeviceCaseCache.foreground_index"), float(threshold))
+        prefix = self._fg_index.get(key)
+        if prefix is None:
+            _require_cuda(self.labels, "DeviceCaseCache.foreground_index")
+            Z, Y, X = self.shape_zyx
+            prefix = torch.empty((len(self), Z * Y + 1), dtype=torch.int32, device=self.labels.device)
+            L.call("sp_fg_row_index", O.ptr(self.labels), len(self), C1, Z, Y, X, _as_i32(key[0]), key[1], O.ptr(prefix), O.stream())
+            self._fg_index[key] = prefix
+        return prefix
 
     @property
     def nbytes(self):
         return sum(t.numel() * t.element_size() for t in (self.images, self.labels, self.clinical) if t is not None)
 
 
-def _gather_launch(cache, table, ext0, pad0, padval0, ext1, pad1):
+def _chanmask(channels, C1, who):
+    """label channels -> the bit mask of the foreground kernels (``None``: all ``C1`` channels)"""
+    if C1 > 32:
+        raise ValueError("%s: %d label channels, the channel mask has 32 bits" % (who, C1))
+    if channels is None:
+        return (1 << C1) - 1
+    mask = 0
+    for c in channels:
+        if not 0 <= int(c) < C1:
+            raise ValueError("%s: channel %d of %d label channels" % (who, int(c), C1))
+        mask |= 1 << int(c)
+    if not mask:
+        raise ValueError("%s: no channel selected" % who)
+    return mask
+
+
+def _as_i32(u):
+    """the 32 bits of an unsigned word as the int32 the C ABI takes"""
+    return u - (1 << 32) if u >= (1 << 31) else u
+
+
+class ForegroundOversample(object):
+    """Foreground oversampling of the patches a ``CachedBatchLoader`` cuts: with probability ``fraction`` (nnU-Net uses a third) a
+    sample's uniformly drawn patch origin is replaced by one that puts a uniformly drawn FOREGROUND voxel of its case at a uniformly
+    drawn position ``j`` of the label patch.  A voxel is foreground when its label exceeds ``threshold`` in one of ``channels``
+    (``None``: any label channel).  The voxel is picked on the device (``sp_patch_origins_fg``, csrc/sp_fgpatch.hip) from the cached
+    labels through ``DeviceCaseCache.foreground_index``: one small launch per batch in front of the gather, no host read.  The
+    origin is ``o = clamp(f - j, 0, padded - patch)`` with ``f`` the voxel in the (flipped) label frame, so the voxel sits at ``j``
+    unless a clamp acts and inside the label patch either way; a case without foreground keeps its uniform origin.  Under a
+    ``PatchAugment`` the voxel sits at ``j`` BEFORE the transform: rotation, scaling and deformation may move it out of the patch,
+    and the guarantee is statistical, not per sample.
+
+    Every draw comes from this object's own ``numpy.random.RandomState(seed)`` -- the same number of draws per batch whatever the
+    tosses say -- never from Python's ``random``: the loader's origin and flip draws stay where they are."""
+
+    def __init__(self, fraction=1.0 / 3.0, channels=None, threshold=0.5, seed=None):
+        if not 0 <= fraction <= 1:
+            raise ValueError("ForegroundOversample: fraction is a probability, got %r" % (fraction,))
+        if channels is not None:
+            channels = [int(c) for c in channels]
+            if any(c < 0 for c in channels) or len(set(channels)) != len(channels):
+                raise ValueError("ForegroundOversample: channels are distinct non-negative label channel indices, got %r" % (channels,))
+            if not channels:
+                raise ValueError("ForegroundOversample: channels is None (all label channels) or a non-empty list")
+        self.fraction, self.channels, self.threshold = float(fraction), channels, float(threshold)
+        if seed is None:
+            seed = datetime.datetime.now().second + datetime.datetime.now().microsecond
+        self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._rs = np.random.RandomState(self._seed & 0xFFFFFFFF)
+
+    def draw(self, B, ext1):
+        """The host draws of one batch, int32 (B, 5): ``force`` (toss < fraction), ``u`` (a uniform 32-bit word, stored as the int32
+        of the same bits), ``jx, jy, jz`` uniform in [0, ext1) per axis."""
+        r = self._rs.random_sample((B, 5))                 # toss, word, three positions: 53-bit fractions k / 2^53
+        ext = np.asarray(ext1, dtype=np.int32)
+        draws = np.empty((B, 5), dtype=np.int32)
+        draws[:, 0] = r[:, 0] < self.fraction
+        draws[:, 1] = (r[:, 1] * 4294967296.0).astype(np.uint32).view(np.int32)      # floor(k / 2^21): every word equally likely
+        draws[:, 2:5] = np.minimum((r[:, 2:5] * ext).astype(np.int32), ext - 1)
+        return draws
+
+
+def _origins_fg_launch(cache, foreground, table_dev, draws_dev, ext1, omax):
+    """``sp_patch_origins_fg`` on the stream of the upload and the gather: rewrites the origins of ``table_dev`` in place"""
+    import ctypes
+    from stroke_prediction_amd.runtime import lib as L, ops as O
+    Z, Y, X = cache.shape_zyx
+    C1 = int(cache.labels.shape[1])
+    mask = _chanmask(foreground.channels, C1, "CachedBatchLoader")
+    prefix = cache.foreground_index(foreground.channels, foreground.threshold)
+    i3 = lambda v: (ctypes.c_int32 * 3)(*[int(a) for a in v])
+    L.call("sp_patch_origins_fg", O.ptr(cache.labels), O.ptr(prefix), len(cache), C1, Z, Y, X, _as_i32(mask), foreground.threshold,
+           O.ptr(draws_dev), i3(ext1), i3(omax), O.ptr(table_dev), None, int(table_dev.shape[0]), O.stream())
+
+
+def _gather_launch(cache, table, ext0, pad0, padval0, ext1, pad1, foreground=None, omax=None):
     """The one ``sp_patch_gather_batch`` launch of a batch: ``table`` (host int32 (B, 5): slot, ox, oy, oz, flip) goes up in one small
-    pinned copy; returns (images (B, C0, d0, h0, w0) or ``[]``, labels (B, C1, d1, h1, w1) or ``[]``, the device table)."""
+    pinned copy; returns (images (B, C0, d0, h0, w0) or ``[]``, labels (B, C1, d1, h1, w1) or ``[]``, the device table).  With
+    ``foreground`` (a ``ForegroundOversample``; ``omax`` = padded - ext0) the same copy also carries its draws and ``sp_patch_origins_fg``
+    rewrites the device table between the copy and the gather."""
     import ctypes
     from stroke_prediction_amd.runtime import lib as L, ops as O
     src0, src1 = cache.images, cache.labels
@@ -607,7 +705,13 @@ def _gather_launch(cache, table, ext0, pad0, padval0, ext1, pad1):
     dev = (src0 if src0 is not None else src1).device
     B = int(table.shape[0])
     Z, Y, X = cache.shape_zyx
-    table_dev = table.pin_memory().to(dev, non_blocking=True)
+    if foreground is None:
+        table_dev = table.pin_memory().to(dev, non_blocking=True)
+    else:
+        host = torch.from_numpy(np.concatenate((table.numpy().reshape(-1), foreground.draw(B, ext1).reshape(-1))))
+        words = host.pin_memory().to(dev, non_blocking=True)
+        table_dev = words[:B * 5].view(B, 5)
+        _origins_fg_launch(cache, foreground, table_dev, words[B * 5:], ext1, omax)
     dst0 = torch.empty((B, src0.shape[1], ext0[2], ext0[1], ext0[0]), dtype=torch.float32, device=dev) if src0 is not None else None
     dst1 = torch.empty((B, src1.shape[1], ext1[2], ext1[1], ext1[0]), dtype=torch.float32, device=dev) if src1 is not None else None
     i3 = lambda v: (ctypes.c_int32 * 3)(*[int(a) for a in v])
@@ -703,9 +807,10 @@ class PatchAugment(object):
         return fields
 
 
-def _sample_launch(cache, table, ext0, pad0, padval0, ext1, pad1, augment):
+def _sample_launch(cache, table, ext0, pad0, padval0, ext1, pad1, augment, foreground=None, omax=None):
     """``_gather_launch`` through ``augment``: one pinned upload carries the table, ``xform`` and ``intensity`` (int32 and fp32 words
-    of one buffer), ``sp_patch_sample_batch`` builds the batch; the noise and filter launches come first when a sample deforms."""
+    of one buffer), ``sp_patch_sample_batch`` builds the batch; the noise and filter launches come first when a sample deforms.
+    ``foreground`` / ``omax``: as for ``_gather_launch``; its draws are the last words of the upload."""
     import ctypes
     from stroke_prediction_amd.runtime import lib as L, ops as O
     src0, src1 = cache.images, cache.labels
@@ -716,15 +821,20 @@ def _sample_launch(cache, table, ext0, pad0, padval0, ext1, pad1, augment):
     C0 = src0.shape[1] if src0 is not None else 0
     draws = augment.draw(B, C0)
     inten = draws["intensity"]
-    host = torch.empty(B * 21 + (B * C0 * 2 if inten is not None else 0), dtype=torch.int32)
+    n_aug = B * 21 + (B * C0 * 2 if inten is not None else 0)
+    host = torch.empty(n_aug + (B * 5 if foreground is not None else 0), dtype=torch.int32)
     host[:B * 5] = table.reshape(-1)
     host[B * 5:B * 21].view(torch.float32).copy_(torch.from_numpy(draws["xform"]).reshape(-1))
     if inten is not None:
-        host[B * 21:].view(torch.float32).copy_(torch.from_numpy(inten).reshape(-1))
+        host[B * 21:n_aug].view(torch.float32).copy_(torch.from_numpy(inten).reshape(-1))
+    if foreground is not None:
+        host[n_aug:].copy_(torch.from_numpy(foreground.draw(B, ext1)).reshape(-1))
     words = host.pin_memory().to(dev, non_blocking=True)
     table_dev = words[:B * 5].view(B, 5)
     xform_dev = words[B * 5:B * 21].view(torch.float32)
-    inten_dev = words[B * 21:].view(torch.float32) if inten is not None else None
+    inten_dev = words[B * 21:n_aug].view(torch.float32) if inten is not None else None
+    if foreground is not None:
+        _origins_fg_launch(cache, foreground, table_dev, words[n_aug:], ext1, omax)
     fields = augment.make_fields(draws, B, (ext0[2], ext0[1], ext0[0]), dev)
     dst0 = torch.empty((B, C0, ext0[2], ext0[1], ext0[0]), dtype=torch.float32, device=dev) if src0 is not None else None
     dst1 = torch.empty((B, src1.shape[1], ext1[2], ext1[1], ext1[0]), dtype=torch.float32, device=dev) if src1 is not None else None
@@ -776,9 +886,18 @@ class CachedBatchLoader(object):
     is ``sp_patch_sample_batch`` and the upload also carries its transforms; the batch dict is the same.  Random draws come from Python's ``random``, per
     sample in the chain's order (``random.random()`` of ``HemisphericFlip``, then ``randint`` for x, y, z of ``RandomPatch``): with
     equal ``random`` state a batch equals the per-sample chain on the same cases bit for bit.  ``ResamplePlaneXY`` was applied
-    when the cache was filled.  ``last_table``: the host copy of the latest batch's table."""
+    when the cache was filled.  ``last_table``: the host copy of the latest batch's table, as drawn; ``last_table_device``: the device
+    table the gather read (reading it synchronises with the stream).
 
-    def __init__(self, cache, items, batch_size, transforms, batch_transform=None, patch_augment=None):
+    ``foreground`` (a ``ForegroundOversample``): the uniform origins are drawn as always -- the ``random`` stream is the same with and
+    without it, and they are the fallback of a case without foreground -- its draws ride in the upload that carries the table, and
+    ``sp_patch_origins_fg`` rewrites the origins of the forced samples on the device between the upload and the gather: two launches
+    per batch instead of one, no host read, no synchronisation.  It needs a ``RandomPatch`` in the chain, labels in the cache and a
+    patch crop no larger than the image padding on every axis (only then does a clamped origin keep the picked voxel inside the
+    label patch).  With a ``patch_augment`` the picked voxel sits at its drawn position before the transform, so the share of
+    patches with foreground is a statistical property there, not a per-sample guarantee."""
+
+    def __init__(self, cache, items, batch_size, transforms, batch_transform=None, patch_augment=None, foreground=None):
         from torch.utils.data.sampler import BatchSampler, SubsetRandomSampler
         self._stages = _parse_chain(transforms)
         missing = [i for i in items if i not in cache.slot_of]
@@ -788,7 +907,8 @@ class CachedBatchLoader(object):
         self.patch_augment = patch_augment
         self.sampler = SubsetRandomSampler(items)
         self.batch_sampler = BatchSampler(self.sampler, batch_size, drop_last=False)
-        self.last_table = None
+        self.foreground = foreground
+        self.last_table = self.last_table_device = None
         Z, Y, X = cache.shape_zyx
         pad, patch = self._stages.get("PadImages"), self._stages.get("RandomPatch")
         self._pad0 = (pad._padx, pad._pady, pad._padz) if pad is not None else (0, 0, 0)
@@ -799,6 +919,17 @@ class CachedBatchLoader(object):
             self._ext1 = (patch._w - 2 * patch._padx, patch._h - 2 * patch._pady, patch._d - 2 * patch._padz)
         else:
             self._ext0, self._ext1 = self._padded, (X, Y, Z)
+        self._omax = tuple(n - e for n, e in zip(self._padded, self._ext0))
+        if foreground is not None:
+            if patch is None:
+                raise ValueError("CachedBatchLoader: foreground oversampling moves the origin of a RandomPatch; the chain has none")
+            if cache.labels is None:
+                raise ValueError("CachedBatchLoader: foreground oversampling reads the cached labels; the cache holds none")
+            _chanmask(foreground.channels, int(cache.labels.shape[1]), "CachedBatchLoader(foreground=...)")
+            crop = (patch._padx, patch._pady, patch._padz)
+            if any(c > p for c, p in zip(crop, self._pad0)):
+                raise ValueError("CachedBatchLoader: foreground oversampling needs RandomPatch's pad %r <= PadImages' pad %r on every axis: "
+                                 "only then does a clamped origin keep the picked voxel inside the label patch" % (crop, self._pad0))
 
     def __len__(self):
         return len(self.batch_sampler)
@@ -825,11 +956,13 @@ class CachedBatchLoader(object):
         cache = self.cache
         table = torch.tensor([self._row(int(i)) for i in items], dtype=torch.int32)
         self.last_table = table
+        fg = (self.foreground, self._omax) if self.foreground is not None else ()
         if self.patch_augment is not None:
             images, labels, table_dev = _sample_launch(cache, table, self._ext0, self._pad0, self._padval0, self._ext1, (0, 0, 0),
-                                                       self.patch_augment)
+                                                       self.patch_augment, *fg)
         else:
-            images, labels, table_dev = _gather_launch(cache, table, self._ext0, self._pad0, self._padval0, self._ext1, (0, 0, 0))
+            images, labels, table_dev = _gather_launch(cache, table, self._ext0, self._pad0, self._padval0, self._ext1, (0, 0, 0), *fg)
+        self.last_table_device = table_dev
         slots = table[:, 0].tolist()
         batch = {KEY_CASE_ID: default_collate([cache.case_ids[s] for s in slots]),
                  KEY_CLINICAL_IDX: default_collate([cache.clinical_idx[s] for s in slots]),
@@ -847,15 +980,16 @@ def _cache_prefix(chains):
     return [found[0]] if found[0] is not None else []
 
 
-def _cached_loaders(modalities, labels, chains, item_lists, batch_size, batch_transforms, patch_augments=None):
+def _cached_loaders(modalities, labels, chains, item_lists, batch_size, batch_transforms, patch_augments=None, foregrounds=None):
     if not torch.cuda.is_available():
         raise RuntimeError("device_cache=True (stroke_prediction_amd) needs a GPU: the case cache lives in device memory and the "
                            "batches are gathered by a HIP kernel; there is no CPU path")
     ds = _dataset(modalities, labels, _cache_prefix(chains), "cuda")
     cache = DeviceCaseCache(ds, "cuda", items=[i for items in item_lists for i in items])
     patch_augments = patch_augments or [None] * len(chains)
-    return [CachedBatchLoader(cache, items, batch_size, chain, bt, pa)
-            for chain, items, bt, pa in zip(chains, item_lists, batch_transforms, patch_augments)]
+    foregrounds = foregrounds or [None] * len(chains)
+    return [CachedBatchLoader(cache, items, batch_size, chain, bt, pa, fg)
+            for chain, items, bt, pa, fg in zip(chains, item_lists, batch_transforms, patch_augments, foregrounds)]
 
 
 def _check_patch_augment(patch_augment, device_cache):
@@ -864,51 +998,62 @@ def _check_patch_augment(patch_augment, device_cache):
                          "(sp_patch_sample_batch); the per-sample chain has no such path")
 
 
+def _check_foreground(foreground, device_cache):
+    if foreground is not None and not device_cache:
+        raise ValueError("foreground needs device_cache=True: the foreground voxel is picked from the labels of the device-resident case "
+                         "cache (sp_patch_origins_fg); the per-sample chain has no such path")
+
+
 def split_data_loader3D(modalities, labels, indices, batch_size, random_seed=None, valid_size=0.5, shuffle=True,
                         num_workers=4, pin_memory=False, train_transform=[], valid_transform=[], batch_transform=None,
-                        device_cache=False, patch_augment=None):
+                        device_cache=False, patch_augment=None, foreground=None):
     """data.py:113-147: one fold -> (training loader, validation loader); the first ``valid_size`` share of the
     (seed-shuffled) fold validates.  ``batch_transform`` (e.g. ``BatchElasticDeform``): applied to every collated TRAINING
     batch; the validation loader never gets it.  ``device_cache``: both loaders are ``CachedBatchLoader``s over one shared
     ``DeviceCaseCache`` (needs a GPU).  ``patch_augment`` (a ``PatchAugment``; needs ``device_cache``): the TRAINING loader samples
-    its patches through it; the validation loader never gets it."""
+    its patches through it; the validation loader never gets it.  ``foreground`` (a ``ForegroundOversample``; needs ``device_cache``):
+    the TRAINING loader forces its share of every batch onto foreground; the validation loader never gets it."""
     assert 0 <= valid_size <= 1, "[!] valid_size should be in the range [0, 1]."
     assert train_transform and valid_transform, "You must provide at least a numpy-to-torch transformation."
     _check_patch_augment(patch_augment, device_cache)
+    _check_foreground(foreground, device_cache)
     dev = _pipeline_device()
     ds_train, ds_valid = _dataset(modalities, labels, train_transform, dev), _dataset(modalities, labels, valid_transform, dev)
     items = _fold_items(ds_train, indices, shuffle, random_seed)
     split = int(np.floor(valid_size * len(items)))
     if device_cache:
         return tuple(_cached_loaders(modalities, labels, [train_transform, valid_transform], [items[split:], items[:split]], batch_size,
-                                     [batch_transform, None], [patch_augment, None]))
+                                     [batch_transform, None], [patch_augment, None], [foreground, None]))
     return (_loader(ds_train, items[split:], batch_size, num_workers, pin_memory, True, batch_transform),
             _loader(ds_valid, items[:split], batch_size, num_workers, pin_memory, False))
 
 
 def single_data_loader3D(modalities, labels, indices, batch_size, random_seed=None, valid_size=0.5, shuffle=True,
                          num_workers=4, pin_memory=False, train_transform=[], batch_transform=None, device_cache=False,
-                         patch_augment=None):
-    """data.py:150-172; ``batch_transform``, ``device_cache``, ``patch_augment``: as for ``split_data_loader3D``."""
+                         patch_augment=None, foreground=None):
+    """data.py:150-172; ``batch_transform``, ``device_cache``, ``patch_augment``, ``foreground``: as for ``split_data_loader3D``."""
     assert train_transform, "You must provide at least a numpy-to-torch transformation."
     _check_patch_augment(patch_augment, device_cache)
+    _check_foreground(foreground, device_cache)
     ds = _dataset(modalities, labels, train_transform, _pipeline_device())
     items = _fold_items(ds, indices, shuffle, random_seed)
     if device_cache:
-        return _cached_loaders(modalities, labels, [train_transform], [items], batch_size, [batch_transform], [patch_augment])[0]
+        return _cached_loaders(modalities, labels, [train_transform], [items], batch_size, [batch_transform], [patch_augment], [foreground])[0]
     return _loader(ds, items, batch_size, num_workers, pin_memory, True, batch_transform)
 
 
 def get_stroke_shape_training_data(modalities, labels, train_transform, valid_transform, fold_indices, ratio, seed=4,
-                                   batchsize=2, split=True, batch_transform=None, device_cache=False, patch_augment=None):
+                                   batchsize=2, split=True, batch_transform=None, device_cache=False, patch_augment=None,
+                                   foreground=None):
     """data.py:175-182 (``num_workers=0``: the transforms run in the training process -- here on its GPU)."""
     if split:
         return split_data_loader3D(modalities, labels, fold_indices, batchsize, random_seed=seed, valid_size=ratio,
                                    train_transform=train_transform, valid_transform=valid_transform, num_workers=0,
-                                   batch_transform=batch_transform, device_cache=device_cache, patch_augment=patch_augment)
+                                   batch_transform=batch_transform, device_cache=device_cache, patch_augment=patch_augment,
+                                   foreground=foreground)
     return single_data_loader3D(modalities, labels, fold_indices, batchsize, random_seed=seed, valid_size=ratio,
                                 train_transform=train_transform, num_workers=0, batch_transform=batch_transform,
-                                device_cache=device_cache, patch_augment=patch_augment), None
+                                device_cache=device_cache, patch_augment=patch_augment, foreground=foreground), None
 
 
 get_stroke_prediction_training_data = get_stroke_shape_training_data      # data.py:185-192: the same factory

@@ -61,6 +61,12 @@ _UNET = [
     ("--patchaugment", dict(action="store_true", default=False,
                             help="(MI355X build) with --devicecache: rotate / scale / elastically deform the training patches and change "
                                  "their intensity inside the kernel that builds the batch (data.PatchAugment, seeded by --seed)")),
+    ("--fgfraction", dict(type=float, default=0.0,
+                          help="(MI355X build) with --devicecache: share of every training batch whose patch is forced to hold a "
+                               "foreground voxel, picked on the device from the cached labels (data.ForegroundOversample, seeded by "
+                               "--seed; nnU-Net uses 0.33); 0 = off")),
+    ("--fgchannels", dict(type=int, nargs="+", default=None,
+                          help="(MI355X build) --fgfraction: the label channels that count as foreground (default: all)")),
 ]
 _SDM = [
     ("unet", dict(type=str, help="Path to model of Segmentation Unet")),
@@ -102,7 +108,8 @@ class CAEParser(ExpParser):
 
 class UnetParser(ExpParser):
     """``--patchaugment`` samples the training patches from the device-resident case cache through a per-sample transform: it
-    goes with ``--devicecache`` (the per-sample chain has no such path)."""
+    goes with ``--devicecache`` (the per-sample chain has no such path).  So does ``--fgfraction``: the foreground voxel is picked
+    from the cached labels."""
     EXTRA = _UNET
 
     def parse_args(self, args=None, namespace=None):
@@ -110,6 +117,11 @@ class UnetParser(ExpParser):
         if ns.patchaugment and not ns.devicecache:
             self.error("--patchaugment needs --devicecache: the augmented patches are sampled from the device-resident case cache "
                        "(sp_patch_sample_batch); the per-sample chain has no such path")
+        if not 0 <= ns.fgfraction <= 1:
+            self.error("--fgfraction is a share of the batch in [0, 1], got %r" % ns.fgfraction)
+        if ns.fgfraction > 0 and not ns.devicecache:
+            self.error("--fgfraction needs --devicecache: the foreground voxel is picked from the labels of the device-resident case "
+                       "cache (sp_patch_origins_fg); the per-sample chain has no such path")
         return ns
 
 

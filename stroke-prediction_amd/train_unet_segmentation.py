@@ -33,9 +33,10 @@ def build_loaders(args):
                      data.PadImages(pad[0], pad[1], pad[2], pad_value=0), data.RandomPatch(*PATCH, pad[0], pad[1], pad[2]),
                      data.ToTensor()]
     augment = data.PatchAugment(seed=args.seed) if args.patchaugment else None
+    foreground = data.ForegroundOversample(args.fgfraction, args.fgchannels, seed=args.seed) if args.fgfraction > 0 else None
     loaders = data.get_stroke_shape_training_data(IMAGE_VOLUMES, LABEL_VOLUMES, chain(), chain(), args.fold, args.validsetsize,
                                                   seed=args.seed, batchsize=args.batchsize, device_cache=args.devicecache,
-                                                  patch_augment=augment)
+                                                  patch_augment=augment, foreground=foreground)
     print('Size training set:', len(loaders[0].sampler.indices), 'samples | Size validation set:', len(loaders[1].sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
     return loaders
