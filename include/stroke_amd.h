@@ -43,7 +43,8 @@ enum { SP_REDUCE_ROWS = 8 };
  * its accumulator sums[SP_REDUCE_ROWS][SP_VLOSS_PITCH(C)], four columns per channel */
 enum { SP_VLOSS_DICE = 1, SP_VLOSS_BCE = 2 };
 #define SP_VLOSS_PITCH(C) ((4 * (C) + 15) / 16 * 16)
-/* the boundary-loss family (sp_bloss_*): the same four columns per channel, the fourth holding sum o*phi */
+/* the boundary-loss entry points (sp_bloss_*; one kernel family with sp_vloss_*): the same four columns per channel, the fourth holding
+ * sum o*phi */
 #define SP_BLOSS_PITCH(C) SP_VLOSS_PITCH(C)
 enum { SP_BF16 = 0, SP_F32 = 1,
        /* bf16 PAIR: value = hi + lo with hi = bf16(value) and lo = bf16(value - hi), stored as TWO bf16 tensors of the same
@@ -788,7 +789,8 @@ int sp_dice_bwd(const float* o, int64_t o_bstride, const float* t, int64_t t_bst
 /* ------------------------------------------------------------------ BCE and Dice + BCE criteria (the `# nn.BCELoss()` the
  * reference's training scripts name beside BatchDiceLoss, e.g. train_unet_segmentation.py:15).  torch.nn.BCELoss semantics:
  *   bce(o, t) = -(t max(log o, -100) + (1 - t) max(log(1 - o), -100)),  d bce / d o = (o - t) / max(o (1 - o), 1e-12)
- * so o exactly 0 or 1 (a saturated fp32 sigmoid) is legal input and gives finite values and gradients.
+ * so o exactly 0 or 1 (a saturated fp32 sigmoid) is legal input and gives finite values and gradients.  sp_vloss_* and sp_bloss_*
+ * (below) are entry points of one kernel family of four moments per channel; they differ in what the fourth holds.
  * sp_vloss_sums: o, t as for sp_dice_sums.  terms: SP_VLOSS_DICE | SP_VLOSS_BCE.  sums[row][4*c + k] (fp64, zeroed by the caller;
  * SP_REDUCE_ROWS replica rows of SP_VLOSS_PITCH(C) doubles) += (sum o*t, sum o*o, sum t*t, sum bce) over batch and volume; the
  * moments of a term that is not asked for are neither computed nor added.  Same reduction order as sp_dice_sums.  16-byte loads when
@@ -805,7 +807,7 @@ int sp_vloss_finalize_clear(double* sums, const float* w_dice, const float* w_bc
  * scalar gradient (NULL = 1).  Channels with cc == 0 skip the division. */
 int sp_vloss_bwd(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* coef, const float* upstream,
                  int32_t B, int32_t C, int64_t DHW, float* dout, sp_stream_t stream);
-/* sp_cae_loss_fwd / _bwd with the criterion chosen by terms: each of the three criterion terms (core, penumbra, lesion) is
+/* sp_cae_loss_fwd / _bwd (the same kernels with terms = SP_VLOSS_DICE and a coef of 8 floats) with the criterion chosen by terms: each of the three criterion terms (core, penumbra, lesion) is
  *   [SP_VLOSS_DICE] (1 - dice_weight (2 I + eps)/(O + T + eps)) + [SP_VLOSS_BCE] bce_weight * mean bce
  * the hinge terms, the latent term and the / (5 + factor) are those of sp_cae_loss_fwd.  sums: SP_REDUCE_ROWS x 16 doubles, zeroed by
  * the caller (columns 0-11 as for sp_cae_loss_fwd, 12-14 the BCE sums of c, p, l); coef: 11 floats (0-7 as for sp_cae_loss_fwd,
@@ -833,8 +835,8 @@ int sp_cae_loss_crit_bwd(const float* c, int64_t cbs, const float* p, int64_t pb
 int sp_signed_distance_batch_workspace(int32_t B, int32_t C, int32_t D, int32_t H, int32_t W, int64_t* floats);
 int sp_signed_distance_batch(const float* t, int64_t t_bstride, int32_t B, int32_t C, int32_t D, int32_t H, int32_t W, float* phi,
                              float* ws, int64_t ws_floats, sp_stream_t stream);
-/* The sp_vloss_* triple with one more input, phi (dense (B, C, DHW), e.g. from sp_signed_distance_batch), and the moment sum o*phi in
- * place of the BCE sum: sums[row][4*c + k] (fp64, zeroed by the caller; SP_REDUCE_ROWS replica rows of SP_BLOSS_PITCH(C) doubles) +=
+/* The kernel family of the sp_vloss_* triple with one more input, phi (dense (B, C, DHW), e.g. from sp_signed_distance_batch), and the
+ * moment sum o*phi in place of the BCE sum: sums[row][4*c + k] (fp64, zeroed by the caller; SP_REDUCE_ROWS replica rows of SP_BLOSS_PITCH(C) doubles) +=
  * (sum o*t, sum o*o, sum t*t, sum o*phi) over batch and volume; dice == 0: only the fourth.  Reduction order and load widths as
  * sp_vloss_sums (16-byte loads need phi + its rows aligned too). */
 int sp_bloss_sums(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* phi, int32_t B, int32_t C,

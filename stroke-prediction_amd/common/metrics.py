@@ -9,14 +9,19 @@ against one target, the points of a time-to-treatment curve -- ``sp_binary_measu
 no host implementation here; the checker is ``oracle/measures.py``.
 
 ``BCELoss`` and ``DiceBCELoss`` -- the ``# nn.BCELoss()`` the reference's training scripts name beside their Dice criterion -- run on
-one kernel family of their own (``sp_vloss_sums`` / ``_finalize_clear`` / ``_bwd``), take the same fused routes as ``BatchDiceLoss``
-(``mean_of_channel_losses``, ``cae_reconstruction_loss``) and are picked by name with ``make_criterion``.
+``sp_vloss_sums`` / ``_finalize_clear`` / ``_bwd``, take the same fused routes as ``BatchDiceLoss`` (``mean_of_channel_losses``,
+``cae_reconstruction_loss``) and are picked by name with ``make_criterion``.
 
 ``BoundaryLoss`` and ``DiceBoundaryLoss`` -- the boundary loss of Kervadec et al. (MIDL 2019), mean(o * phi(t)) with phi the signed
 Euclidean distance map of the label, alone or added to Dice with a weight that can grow over the epochs -- compute phi per sample
 and channel on the device (``sp_signed_distance_batch``) and run on ``sp_bloss_sums`` / ``_finalize_clear`` / ``_bwd``; they take the
 ``mean_of_channel_losses`` route, and the CAE learners compose them literally.
+
+All five criteria are ONE autograd function, ``_CriterionFn``, driven by a record per kernel family (``_FAMILIES``: ``sp_dice_*``,
+``sp_vloss_*``, ``sp_bloss_*``), with one registry of accumulators, ``_CRIT_SUMS``.
 """
+import collections
+
 import numpy
 import torch
 from torch.nn.modules.loss import _Loss as LossModule
@@ -79,52 +84,77 @@ def batch_mean(t):
     return torch.mean(t)
 
 
-_DICE_SUMS = {}      # (device, C, stream) -> [replica rows of the Dice sums (zero between calls), busy]
+_Family = collections.namedtuple("_Family", "sums finalize bwd pitch ncoef select fourth phi")
+# The kernel families of the per-channel criteria, one record each: the three entry points; the accumulator's row pitch (doubles) for C
+# channels; the coefficients per channel; ``select``: the integer the sums call takes behind DHW; ``fourth``: there is a fourth moment --
+# finalize takes a second weight vector and the element count; ``phi``: the signed-distance map of the targets is a third operand of
+# sums and backward, and finalize takes the device scalar that scales the fourth moment's weights.
+_FAMILIES = {
+    "dice": _Family("sp_dice_sums", "sp_dice_finalize_clear", "sp_dice_bwd", lambda L, C: (3 * C + 15) // 16 * 16, 2,
+                    lambda L, w_dice, w4: (), False, False),
+    "vloss": _Family("sp_vloss_sums", "sp_vloss_finalize_clear", "sp_vloss_bwd", lambda L, C: L.SP_VLOSS_PITCH(C), 3,
+                     lambda L, w_dice, w4: ((L.SP_VLOSS_DICE if w_dice is not None else 0) | (L.SP_VLOSS_BCE if w4 is not None else 0),),
+                     True, False),
+    "bloss": _Family("sp_bloss_sums", "sp_bloss_finalize_clear", "sp_bloss_bwd", lambda L, C: L.SP_BLOSS_PITCH(C), 3,
+                     lambda L, w_dice, w4: (0 if w_dice is None else 1,), True, True),
+}
+_CRIT_SUMS = {}      # (family, device, C, stream) -> [replica rows of that family's sums (zero between calls), busy]
 
 
-class _DiceFn(torch.autograd.Function):
-    """loss = 1 - sum_c w_c (2 I_c + eps) / (O_c + T_c + eps); sums over batch and volume per channel.  Three HIP
-    launches forward (sums, finalize) and one backward; the scalar algebra never leaves the device."""
+class _CriterionFn(torch.autograd.Function):
+    """loss = [1 - sum_c wd_c (2 I_c + eps) / (O_c + T_c + eps)] + [sum_c w4_c * scale * mean_c X], either bracket absent when its
+    weights are None; sums and means over batch and volume per channel.  ``family`` names the kernels: "dice" (the first bracket only),
+    "vloss" (X = bce(o, t) with torch.nn.BCELoss semantics) or "bloss" (X = o * phi, phi = signed_distance_batch(targets), scale a
+    one-float device tensor read by the finalize kernel: a captured step follows its schedule).  Two HIP launches forward (sums,
+    finalize) behind the signed-distance ones, and one backward; the scalar algebra never leaves the device.  In the exact
+    data-parallel mode the sums are all-reduced and the element count is the global one: the local backward yields this rank's share
+    of the whole-batch gradient (as _GlobalMeanFn); phi is local."""
 
     @staticmethod
-    def forward(ctx, outputs, targets, weights, eps):
+    def forward(ctx, family, outputs, targets, w_dice, w4, scale, eps):
         from stroke_prediction_amd.runtime import lib as L, ops as O
+        from stroke_prediction_amd.runtime.layers import SYNC, _allreduce
+        fam = _FAMILIES[family]
         o, obs = _batch_strided(outputs)
         t, tbs = _batch_strided(targets)
         B, C = o.shape[0], o.shape[1]
         dhw = o.numel() // (B * C)
-        # ONE accumulator per (device, C), zeroed once: sp_dice_finalize_clear leaves it zero again (no fill launch per call -- 5 us of a
+        phi = [signed_distance_batch(t)] if fam.phi else []
+        # ONE accumulator per (family, device, C), zeroed once: finalize_clear leaves it zero again (no fill launch per call -- 5 us of a
         # captured step's dependent chain).  ``busy``: a call that died between the two launches left sums behind -> zero them here.
-        key = (o.device, C, int(torch.cuda.current_stream(o.device).cuda_stream))      # (per stream: launches of one stream are ordered)
-        ent = _DICE_SUMS.get(key)
+        key = (family, o.device, C, int(torch.cuda.current_stream(o.device).cuda_stream))      # (per stream: launches of one stream are ordered)
+        ent = _CRIT_SUMS.get(key)
         if ent is None or ent[1]:
-            ent = _DICE_SUMS[key] = [torch.zeros(L.SP_REDUCE_ROWS, (3 * C + 15) // 16 * 16, dtype=torch.float64, device=o.device), False]
+            ent = _CRIT_SUMS[key] = [torch.zeros(L.SP_REDUCE_ROWS, fam.pitch(L, C), dtype=torch.float64, device=o.device), False]
         sums = ent[0]   # replica rows
         ent[1] = True
-        L.call("sp_dice_sums", O.ptr(o), obs, O.ptr(t), tbs, B, C, dhw, O.ptr(sums), O.stream())
-        from stroke_prediction_amd.runtime.layers import SYNC, _allreduce
-        if SYNC["on"]:                  # Dice is a ratio of WHOLE-batch sums (metrics.py:24-27): make them global
+        L.call(fam.sums, O.ptr(o), obs, O.ptr(t), tbs, *[O.ptr(p) for p in phi], B, C, dhw, *fam.select(L, w_dice, w4), O.ptr(sums), O.stream())
+        count = float(B * dhw)
+        if SYNC["on"]:                  # ratios and means of WHOLE-batch sums (metrics.py:24-27): make them global
             _allreduce(sums)
-        w = _weights_on(o.device, weights)      # cached: no host->device copy inside a (graph-captured) step
+            count *= SYNC["world"]
+        # cached weights: no host->device copy inside a (graph-captured) step
+        ws = [None if w is None else O.ptr(_weights_on(o.device, w)) for w in ((w_dice, w4) if fam.fourth else (w_dice,))]
         loss = torch.empty((), dtype=torch.float32, device=o.device)
-        coef = torch.empty(2 * C, dtype=torch.float32, device=o.device)
-        L.call("sp_dice_finalize_clear", O.ptr(sums), O.ptr(w), float(eps), C, O.ptr(loss), O.ptr(coef), O.stream())
+        coef = torch.empty(fam.ncoef * C, dtype=torch.float32, device=o.device)
+        L.call(fam.finalize, O.ptr(sums), *ws, *([O.ptr(scale)] if fam.phi else []), float(eps), *([count] if fam.fourth else []), C,
+               O.ptr(loss), O.ptr(coef), O.stream())
         ent[1] = False
-        ctx.save_for_backward(o, t, coef)
-        ctx.strides = (obs, tbs)
+        ctx.save_for_backward(o, t, *phi, coef)
+        ctx.family, ctx.strides = family, (obs, tbs)
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
         from stroke_prediction_amd.runtime import lib as L, ops as O
-        o, t, coef = ctx.saved_tensors
+        o, t, *phi, coef = ctx.saved_tensors
         obs, tbs = ctx.strides
         B, C = o.shape[0], o.shape[1]
         up = gloss if (gloss.dtype == torch.float32 and gloss.is_contiguous()) else gloss.float().contiguous()
         d = torch.empty(o.shape, dtype=torch.float32, device=o.device)
-        L.call("sp_dice_bwd", O.ptr(o), obs, O.ptr(t), tbs, O.ptr(coef), O.ptr(up), B, C, o.numel() // (B * C), O.ptr(d),
-               O.stream())
-        return d, None, None, None
+        L.call(_FAMILIES[ctx.family].bwd, O.ptr(o), obs, O.ptr(t), tbs, *[O.ptr(p) for p in phi], O.ptr(coef), O.ptr(up), B, C,
+               o.numel() // (B * C), O.ptr(d), O.stream())
+        return None, d, None, None, None, None, None
 
 
 class BatchDiceLoss(LossModule):
@@ -141,60 +171,7 @@ class BatchDiceLoss(LossModule):
         assert outputs.shape == targets.shape
         if not outputs.is_cuda or self._dim != 1:
             raise RuntimeError("BatchDiceLoss (stroke_prediction_amd) runs on the GPU with channel dim 1 only")
-        return _DiceFn.apply(outputs, targets, tuple(float(w) for w in self._label_weights), float(self._epsilon))
-
-
-_VLOSS_SUMS = {}     # (device, C, stream) -> [replica rows of the voxel-loss sums (zero between calls), busy]
-
-
-class _VoxelLossFn(torch.autograd.Function):
-    """loss = [1 - sum_c wd_c (2 I_c + eps) / (O_c + T_c + eps)] + [sum_c wb_c mean_c bce(o, t)], either bracket absent when its
-    weights are None; sums and means over batch and volume per channel, bce with torch.nn.BCELoss semantics.  Shaped like _DiceFn:
-    two HIP launches forward (sums, finalize) and one backward.  In the exact data-parallel mode the sums are all-reduced and the
-    element count is the global one: the local backward yields this rank's share of the whole-batch gradient (as _GlobalMeanFn)."""
-
-    @staticmethod
-    def forward(ctx, outputs, targets, w_dice, w_bce, eps):
-        from stroke_prediction_amd.runtime import lib as L, ops as O
-        from stroke_prediction_amd.runtime.layers import SYNC, _allreduce
-        o, obs = _batch_strided(outputs)
-        t, tbs = _batch_strided(targets)
-        B, C = o.shape[0], o.shape[1]
-        dhw = o.numel() // (B * C)
-        terms = (L.SP_VLOSS_DICE if w_dice is not None else 0) | (L.SP_VLOSS_BCE if w_bce is not None else 0)
-        # one accumulator per (device, C, stream), left zero by sp_vloss_finalize_clear; ``busy`` as in _DiceFn
-        key = (o.device, C, int(torch.cuda.current_stream(o.device).cuda_stream))
-        ent = _VLOSS_SUMS.get(key)
-        if ent is None or ent[1]:
-            ent = _VLOSS_SUMS[key] = [torch.zeros(L.SP_REDUCE_ROWS, L.SP_VLOSS_PITCH(C), dtype=torch.float64, device=o.device), False]
-        sums = ent[0]
-        ent[1] = True
-        L.call("sp_vloss_sums", O.ptr(o), obs, O.ptr(t), tbs, B, C, dhw, terms, O.ptr(sums), O.stream())
-        count = float(B * dhw)
-        if SYNC["on"]:                  # whole-batch sums and a whole-batch mean
-            _allreduce(sums)
-            count *= SYNC["world"]
-        wd = None if w_dice is None else _weights_on(o.device, w_dice)      # cached: no host->device copy inside a captured step
-        wb = None if w_bce is None else _weights_on(o.device, w_bce)
-        loss = torch.empty((), dtype=torch.float32, device=o.device)
-        coef = torch.empty(3 * C, dtype=torch.float32, device=o.device)
-        L.call("sp_vloss_finalize_clear", O.ptr(sums), None if wd is None else O.ptr(wd), None if wb is None else O.ptr(wb), float(eps),
-               count, C, O.ptr(loss), O.ptr(coef), O.stream())
-        ent[1] = False
-        ctx.save_for_backward(o, t, coef)
-        ctx.strides = (obs, tbs)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gloss):
-        from stroke_prediction_amd.runtime import lib as L, ops as O
-        o, t, coef = ctx.saved_tensors
-        obs, tbs = ctx.strides
-        B, C = o.shape[0], o.shape[1]
-        up = gloss if (gloss.dtype == torch.float32 and gloss.is_contiguous()) else gloss.float().contiguous()
-        d = torch.empty(o.shape, dtype=torch.float32, device=o.device)
-        L.call("sp_vloss_bwd", O.ptr(o), obs, O.ptr(t), tbs, O.ptr(coef), O.ptr(up), B, C, o.numel() // (B * C), O.ptr(d), O.stream())
-        return d, None, None, None, None
+        return _CriterionFn.apply("dice", outputs, targets, tuple(float(w) for w in self._label_weights), None, None, float(self._epsilon))
 
 
 def _check_voxel_loss_inputs(name, outputs, targets, label_weights):
@@ -221,7 +198,7 @@ class BCELoss(LossModule):
 
     def forward(self, outputs, targets):
         _check_voxel_loss_inputs("BCELoss", outputs, targets, self._label_weights)
-        return _VoxelLossFn.apply(outputs, targets, None, self.weights(outputs.shape[1]), 0.0)
+        return _CriterionFn.apply("vloss", outputs, targets, None, self.weights(outputs.shape[1]), None, 0.0)
 
 
 class DiceBCELoss(LossModule):
@@ -237,11 +214,8 @@ class DiceBCELoss(LossModule):
     def forward(self, outputs, targets):
         _check_voxel_loss_inputs("DiceBCELoss", outputs, targets, self._label_weights)
         C = outputs.shape[1]
-        return _VoxelLossFn.apply(outputs, targets, tuple(float(w) for w in self._label_weights),
-                                  (float(self._bce_weight) / C,) * C, float(self._epsilon))
-
-
-_BLOSS_SUMS = {}     # (device, C, stream) -> [replica rows of the boundary-loss sums (zero between calls), busy]
+        return _CriterionFn.apply("vloss", outputs, targets, tuple(float(w) for w in self._label_weights),
+                                  (float(self._bce_weight) / C,) * C, None, float(self._epsilon))
 
 
 def signed_distance_workspace_floats(B, C, D, H, W):
@@ -268,58 +242,6 @@ def signed_distance_batch(targets):
     ws = torch.empty(nws, dtype=torch.float32, device=t.device)
     L.call("sp_signed_distance_batch", O.ptr(t), tbs, B, C, D, H, W, O.ptr(phi), O.ptr(ws), nws, O.stream())
     return phi
-
-
-class _BoundaryLossFn(torch.autograd.Function):
-    """loss = [1 - sum_c wd_c (2 I_c + eps) / (O_c + T_c + eps)] + sum_c wb_c * scale * mean_c(o * phi), the Dice bracket absent when
-    its weights are None; phi = signed_distance_batch(targets), scale a one-float device tensor read by the finalize kernel (a
-    captured step follows its schedule).  Shaped like _VoxelLossFn: the signed-distance launches, sums and finalize forward, one
-    launch backward.  In the exact data-parallel mode the sums are all-reduced and the element count is the global one; phi is
-    local."""
-
-    @staticmethod
-    def forward(ctx, outputs, targets, w_dice, w_boundary, scale, eps):
-        from stroke_prediction_amd.runtime import lib as L, ops as O
-        from stroke_prediction_amd.runtime.layers import SYNC, _allreduce
-        o, obs = _batch_strided(outputs)
-        t, tbs = _batch_strided(targets)
-        B, C = o.shape[0], o.shape[1]
-        dhw = o.numel() // (B * C)
-        phi = signed_distance_batch(t)
-        # one accumulator per (device, C, stream), left zero by sp_bloss_finalize_clear; ``busy`` as in _DiceFn
-        key = (o.device, C, int(torch.cuda.current_stream(o.device).cuda_stream))
-        ent = _BLOSS_SUMS.get(key)
-        if ent is None or ent[1]:
-            ent = _BLOSS_SUMS[key] = [torch.zeros(L.SP_REDUCE_ROWS, L.SP_BLOSS_PITCH(C), dtype=torch.float64, device=o.device), False]
-        sums = ent[0]
-        ent[1] = True
-        L.call("sp_bloss_sums", O.ptr(o), obs, O.ptr(t), tbs, O.ptr(phi), B, C, dhw, 0 if w_dice is None else 1, O.ptr(sums), O.stream())
-        count = float(B * dhw)
-        if SYNC["on"]:                  # whole-batch sums and a whole-batch mean
-            _allreduce(sums)
-            count *= SYNC["world"]
-        wd = None if w_dice is None else _weights_on(o.device, w_dice)      # cached: no host->device copy inside a captured step
-        wb = _weights_on(o.device, w_boundary)
-        loss = torch.empty((), dtype=torch.float32, device=o.device)
-        coef = torch.empty(3 * C, dtype=torch.float32, device=o.device)
-        L.call("sp_bloss_finalize_clear", O.ptr(sums), None if wd is None else O.ptr(wd), O.ptr(wb), O.ptr(scale), float(eps), count, C,
-               O.ptr(loss), O.ptr(coef), O.stream())
-        ent[1] = False
-        ctx.save_for_backward(o, t, phi, coef)
-        ctx.strides = (obs, tbs)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gloss):
-        from stroke_prediction_amd.runtime import lib as L, ops as O
-        o, t, phi, coef = ctx.saved_tensors
-        obs, tbs = ctx.strides
-        B, C = o.shape[0], o.shape[1]
-        up = gloss if (gloss.dtype == torch.float32 and gloss.is_contiguous()) else gloss.float().contiguous()
-        d = torch.empty(o.shape, dtype=torch.float32, device=o.device)
-        L.call("sp_bloss_bwd", O.ptr(o), obs, O.ptr(t), tbs, O.ptr(phi), O.ptr(coef), O.ptr(up), B, C, o.numel() // (B * C), O.ptr(d),
-               O.stream())
-        return d, None, None, None, None, None
 
 
 class _ScheduledBoundaryWeight(object):
@@ -376,7 +298,7 @@ class BoundaryLoss(LossModule, _ScheduledBoundaryWeight):
 
     def forward(self, outputs, targets):
         _check_voxel_loss_inputs("BoundaryLoss", outputs, targets, self._label_weights)
-        return _BoundaryLossFn.apply(outputs, targets, None, self.weights(outputs.shape[1]), self._scale_on(outputs.device), 0.0)
+        return _CriterionFn.apply("bloss", outputs, targets, None, self.weights(outputs.shape[1]), self._scale_on(outputs.device), 0.0)
 
 
 class DiceBoundaryLoss(LossModule, _ScheduledBoundaryWeight):
@@ -393,8 +315,8 @@ class DiceBoundaryLoss(LossModule, _ScheduledBoundaryWeight):
     def forward(self, outputs, targets):
         _check_voxel_loss_inputs("DiceBoundaryLoss", outputs, targets, self._label_weights)
         C = outputs.shape[1]
-        return _BoundaryLossFn.apply(outputs, targets, tuple(float(w) for w in self._label_weights), (1.0 / C,) * C,
-                                     self._scale_on(outputs.device), float(self._epsilon))
+        return _CriterionFn.apply("bloss", outputs, targets, tuple(float(w) for w in self._label_weights), (1.0 / C,) * C,
+                                  self._scale_on(outputs.device), float(self._epsilon))
 
 
 def _single_label_boundary_terms(criterion):
@@ -448,15 +370,15 @@ def configure_criterion(criterion, args):
 
 
 class _CaeLossFn(torch.autograd.Function):
-    """CaeReconstructionLearner.loss_step (reference :52-70) as three HIP launches (sp_cae_loss_fwd / _bwd) instead of ~60 torch and
-    Dice kernels: [ mean(|p-i|-(p-i)) + mean(|p-c|-(p-c)) + Dice(c) + Dice(p) + Dice(l) + f mean|zi - zl| ] / (5 + f).  The four
-    gradients come back as consecutive slices of ONE tensor in the order the reconstructions lie in memory, so that a decoder
-    call that produced them stacked on the batch axis (Cae3D._StackManyFn) takes the buffer as it is."""
+    """CaeReconstructionLearner.loss_step (reference :52-70) as three HIP launches (sp_cae_loss_crit_fwd / _bwd) instead of ~60 torch and
+    criterion kernels: [ mean(|p-i|-(p-i)) + mean(|p-c|-(p-c)) + crit(c) + crit(p) + crit(l) + f mean|zi - zl| ] / (5 + f), crit =
+    BatchDiceLoss, BCELoss or DiceBCELoss.  The four gradients come back as consecutive slices of ONE tensor in the order the
+    reconstructions lie in memory, so that a decoder call that produced them stacked on the batch axis (Cae3D._StackManyFn) takes the
+    buffer as it is."""
 
     @staticmethod
     def forward(ctx, c, p, l, i, tc, tp, tl, zi, zl, factor, weight, eps, bce_weight=None):
         from stroke_prediction_amd.runtime import lib as L, ops as O
-        crit = bce_weight is not None            # BCELoss / DiceBCELoss: sp_cae_loss_crit_* (weight None = no Dice term)
         recs = [_batch_strided(t) for t in (c, p, l, i)]
         gts = [_batch_strided(t) for t in (tc, tp, tl)]
         zi_, zl_ = zi.contiguous().float(), zl.contiguous().float()
@@ -465,18 +387,14 @@ class _CaeLossFn(torch.autograd.Function):
         dev = c.device
         sums = torch.zeros(L.SP_REDUCE_ROWS, 16, dtype=torch.float64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        coef = torch.empty(11 if crit else 8, dtype=torch.float32, device=dev)
+        coef = torch.empty(11, dtype=torch.float32, device=dev)
         args = []
         for t, bs in recs + gts:
             args += [O.ptr(t), bs]
-        if crit:
-            L.call("sp_cae_loss_crit_fwd", *args, B, dhw, O.ptr(zi_), O.ptr(zl_), zi_.numel(), float(weight or 0.0), float(bce_weight),
-                   (L.SP_VLOSS_DICE if weight is not None else 0) | L.SP_VLOSS_BCE, float(eps), float(factor), O.ptr(sums), O.ptr(loss), O.ptr(coef),
-                   O.stream())
-        else:
-            L.call("sp_cae_loss_fwd", *args, B, dhw, O.ptr(zi_), O.ptr(zl_), zi_.numel(), float(weight), float(eps), float(factor),
-                   O.ptr(sums), O.ptr(loss), O.ptr(coef), O.stream())
-        ctx.crit = crit
+        # weight / bce_weight None = no Dice / no BCE term
+        terms = (L.SP_VLOSS_DICE if weight is not None else 0) | (L.SP_VLOSS_BCE if bce_weight is not None else 0)
+        L.call("sp_cae_loss_crit_fwd", *args, B, dhw, O.ptr(zi_), O.ptr(zl_), zi_.numel(), float(weight or 0.0), float(bce_weight or 0.0), terms,
+               float(eps), float(factor), O.ptr(sums), O.ptr(loss), O.ptr(coef), O.stream())
         ctx.save_for_backward(*[t for t, _ in recs + gts], zi_, zl_, coef)
         ctx.strides = [bs for _, bs in recs + gts]
         ctx.shapes = (tuple(c.shape), tuple(zi.shape), tuple(zl.shape))
@@ -499,7 +417,7 @@ class _CaeLossFn(torch.autograd.Function):
         args = []
         for t, bs in zip(ts, ctx.strides):
             args += [O.ptr(t), bs]
-        L.call("sp_cae_loss_crit_bwd" if ctx.crit else "sp_cae_loss_bwd", *args, B, dhw, O.ptr(coef), O.ptr(up), O.ptr(d[0]), O.ptr(d[1]),
+        L.call("sp_cae_loss_crit_bwd", *args, B, dhw, O.ptr(coef), O.ptr(up), O.ptr(d[0]), O.ptr(d[1]),
                O.ptr(d[2]), O.ptr(d[3]), O.ptr(zi_), O.ptr(zl_), zi_.numel(), O.ptr(dzi), O.ptr(dzl), O.stream())
         return d[0], d[1], d[2], d[3], None, None, None, dzi.view(ctx.shapes[1]), dzl.view(ctx.shapes[2]), None, None, None, None
 
@@ -510,7 +428,7 @@ def cae_reconstruction_loss(rec, gt, lat, factor, criterion):
     import os
     from stroke_prediction_amd.runtime.layers import SYNC
     ts = (rec.core, rec.penu, rec.lesion, rec.interpolation, gt.core, gt.penu, gt.lesion)
-    terms = _single_label_terms(criterion)       # BatchDiceLoss -> sp_cae_loss_fwd, BCELoss / DiceBCELoss -> sp_cae_loss_crit_fwd
+    terms = _single_label_terms(criterion)       # BatchDiceLoss, BCELoss or DiceBCELoss of one label class
     if os.environ.get("SP_CAE_FUSED_LOSS", "1") == "0" or SYNC["on"] or terms is None or any(t is None or not t.is_cuda or t.dim() != 5 or t.shape[1] != 1 or t.shape != ts[0].shape for t in ts) \
             or lat.interpolation is None or lat.lesion is None or lat.interpolation.shape != lat.lesion.shape:
         return None
@@ -545,21 +463,16 @@ def mean_of_channel_losses(criterion, outputs, targets):
     sp_signed_distance_batch and the sp_bloss_* kernels (one signed-distance set for all n channels).  Anything else: the literal
     sum of calls."""
     n = len(outputs)
-    bterms = _single_label_boundary_terms(criterion)
-    if bterms is not None and n > 1 and outputs[0].is_cuda and outputs[0].dim() == 5:
+    family, terms = "bloss", _single_label_boundary_terms(criterion)
+    if terms is None:
+        terms = _single_label_terms(criterion)
+        family = "dice" if terms is not None and terms[1] is None else "vloss"
+    if terms is not None and n > 1 and outputs[0].is_cuda and (family != "bloss" or outputs[0].dim() == 5):
         ob, tb = _stacked_base(outputs), _stacked_base(targets)
         if ob is not None and tb is not None:
-            w_dice, w_bnd, eps = bterms
-            return _BoundaryLossFn.apply(ob, tb, None if w_dice is None else (w_dice / n,) * n, (w_bnd / n,) * n,
-                                         criterion._scale_on(ob.device), eps)
-    terms = _single_label_terms(criterion)
-    if terms is not None and n > 1 and outputs[0].is_cuda:
-        ob, tb = _stacked_base(outputs), _stacked_base(targets)
-        if ob is not None and tb is not None:
-            w_dice, w_bce, eps = terms
-            if w_bce is None:
-                return _DiceFn.apply(ob, tb, (w_dice / n,) * n, eps)
-            return _VoxelLossFn.apply(ob, tb, None if w_dice is None else (w_dice / n,) * n, (w_bce / n,) * n, eps)
+            w_dice, w4, eps = terms
+            return _CriterionFn.apply(family, ob, tb, None if w_dice is None else (w_dice / n,) * n, None if w4 is None else (w4 / n,) * n,
+                                      criterion._scale_on(ob.device) if family == "bloss" else None, eps)
     total = criterion(outputs[0], targets[0])
     for o, t in zip(outputs[1:], targets[1:]):
         total = total + criterion(o, t)

@@ -281,7 +281,7 @@ def test_criteria_modules_against_the_oracle_and_bit_identical_twice(name):
         od = o.to(DEV)
         parts = float(metrics.BatchDiceLoss([0.3, 0.7])(od, td)) + 0.2 * float(metrics.BoundaryLoss()(od, td))
         assert abs(float(loss) - parts) <= 2 * loss_tolerance(ref_sums, mag, w_dice, w_bnd, scale, o.numel() // 2) + 1e-6
-    for ent in metrics._BLOSS_SUMS.values():
+    for ent in (e for k, e in metrics._CRIT_SUMS.items() if k[0] == "bloss"):
         assert not ent[1] and torch.count_nonzero(ent[0]) == 0
 
 
@@ -357,8 +357,8 @@ def test_weight_follows_a_replayed_graph():
     with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
         loss = crit(static_o, td)
         grad, = torch.autograd.grad(loss, static_o)
-    key = (static_o.device, 2, int(side.cuda_stream))
-    assert key in metrics._BLOSS_SUMS
+    key = ("bloss", static_o.device, 2, int(side.cuda_stream))
+    assert key in metrics._CRIT_SUMS
     for weight in (0.01, 0.5, 0.01):
         crit.set_boundary_weight(weight)
         assert crit.boundary_weight() == weight
@@ -367,7 +367,7 @@ def test_weight_follows_a_replayed_graph():
         print("replay at weight", weight, float(loss), "eager", float(want[weight][0]))
         assert torch.equal(loss, want[weight][0]), (weight, float(loss), float(want[weight][0]))
         assert torch.equal(grad, want[weight][1])
-        assert torch.count_nonzero(metrics._BLOSS_SUMS[key][0]) == 0 and not metrics._BLOSS_SUMS[key][1]
+        assert torch.count_nonzero(metrics._CRIT_SUMS[key][0]) == 0 and not metrics._CRIT_SUMS[key][1]
     assert not torch.equal(want[0.01][1], want[0.5][1])
     ref = R.loss_oracle(o, t, phi, [0.3, 0.7], [0.5, 0.5], 0.5)
     assert abs(float(want[0.5][0]) - ref[2]) <= loss_tolerance(ref[0], ref[1], [0.3, 0.7], [0.5, 0.5], 0.5, o.numel() // 2)

@@ -139,6 +139,112 @@ def test_vloss_kernels_against_the_oracle(shape, terms):
         check_vloss(o, t, shifted, td, terms)
 
 
+# (name, shape, view): dense aligned -> 16-byte loads on 48 of a workgroup's lanes; dense, 105 voxels -> element loads, lanes without a
+# trip; channels 1..2 of a three-channel tensor that starts one float into its allocation -> a length that would take 16-byte loads on
+# row bases that do not (batch stride 3 * 192)
+FALLBACK_CASES = [("aligned", (2, 2, 4, 6, 8), False), ("unaligned", (2, 2, 3, 5, 7), False), ("view", (2, 3, 4, 6, 8), True)]
+
+
+def _fallback_operands(host, view):
+    """the device copy of ``host`` the case asks for, and the host tensor the oracle is fed"""
+    if not view:
+        return host.to(DEV), host
+    buf = torch.empty(host.numel() + 4, device=DEV)
+    dev = buf[1:1 + host.numel()].view(host.shape).copy_(host.to(DEV))[:, 1:3]
+    assert dev.data_ptr() % 16 == 4 and dev[0, 0].numel() % 4 == 0 and dev.stride(0) == 3 * dev[0, 0].numel()
+    return dev, host[:, 1:3]
+
+
+@pytest.mark.parametrize("kind", ["dice", "bce", "dicebce", "boundary", "diceboundary"])
+@pytest.mark.parametrize("case", FALLBACK_CASES, ids=[c[0] for c in FALLBACK_CASES])
+def test_merged_kernels_choose_the_load_width(case, kind):
+    """every instance of the one sums and the one backward template (fourth column absent, BCE, o * phi; with and without Dice) on
+    both load widths and on a strided view, against the fp64 oracles and at the tolerances of test_vloss_kernels_against_the_oracle
+    and test_bloss_kernels_against_the_oracle.  Those two cover dense aligned and dense odd lengths of several workgroups and a channel
+    slice of an odd length; none of them has a workgroup with idle lanes on 16-byte loads or a view whose length is a multiple of four
+    on misaligned rows, so no combination is left out here."""
+    import test_gpu_boundary as TB
+    _, shape, view = case
+    if kind in ("boundary", "diceboundary"):
+        o, t, phi = TB.loss_inputs(shape)
+        (od, oh), (td, th) = _fallback_operands(o, view), _fallback_operands(t, view)
+        ph = phi[:, 1:3] if view else phi
+        assert 0 < float(th.sum()) < th.numel()
+        TB.check_bloss(oh, th, ph, od, td, ph.contiguous().to(DEV), kind)      # phi is dense in every case
+    else:
+        o, t = inputs(shape)
+        (od, oh), (td, th) = _fallback_operands(o, view), _fallback_operands(t, view)
+        check_vloss(oh, th, od, td, {"dice": 1, "bce": 2, "dicebce": 3}[kind])
+
+
+# (B, (D, H, W), latent elements): 210 voxels = one partial workgroup and no latent row; 14760 voxels = eight workgroups along x
+CAE_CASES = [(2, (5, 6, 7), 0), (2, (9, 40, 41), 37)]
+
+
+@functools.lru_cache(maxsize=None)
+def cae_inputs(B, dims, nlat):
+    """host tensors: the four reconstructions stacked on the batch axis, three binary ground truths, two latents (or None)"""
+    g = torch.Generator().manual_seed(11 + nlat)
+    stacked = torch.rand(4 * B, 1, *dims, generator=g)
+    gts = tuple((torch.rand(B, 1, *dims, generator=g) > 0.6).float() for _ in range(3))
+    lat = tuple(torch.randn(nlat, generator=g) for _ in range(2)) if nlat else (None, None)
+    return stacked, gts, lat
+
+
+def run_cae(crit, B, dims, nlat, coef):
+    """sp_cae_loss_fwd / _bwd, or (crit) sp_cae_loss_crit_fwd / _bwd with terms = SP_VLOSS_DICE, on the inputs of cae_inputs with the
+    reconstructions read in place as slices of the stacked tensor; coef: the caller's buffer -> loss, the six gradients"""
+    from stroke_prediction_amd.runtime import lib as L, ops as O
+    stacked, gts, lat = cae_inputs(B, dims, nlat)
+    stacked = stacked.to(DEV)
+    ts = [stacked[k * B:(k + 1) * B] for k in range(4)] + [t.to(DEV) for t in gts]
+    z = [None if x is None else x.to(DEV) for x in lat]
+    dhw = ts[0][0].numel()
+    args = []
+    for t in ts:
+        args += [O.ptr(t), t.stride(0)]
+    zp = [None if x is None else O.ptr(x) for x in z]
+    sums = torch.zeros(L.SP_REDUCE_ROWS, 16, dtype=torch.float64, device=DEV)
+    loss = torch.full((), float("nan"), device=DEV)
+    weights = [0.8, 0.0, L.SP_VLOSS_DICE] if crit else [0.8]
+    L.call("sp_cae_loss_crit_fwd" if crit else "sp_cae_loss_fwd", *args, B, dhw, *zp, nlat, *weights, EPS, 0.36, O.ptr(sums), O.ptr(loss),
+           O.ptr(coef), O.stream())
+    d = [torch.full((B, dhw), float("nan"), device=DEV) for _ in range(4)]
+    dz = [torch.full((nlat,), float("nan"), device=DEV) for _ in range(2)]
+    up = torch.tensor(0.7, device=DEV)
+    L.call("sp_cae_loss_crit_bwd" if crit else "sp_cae_loss_bwd", *args, B, dhw, O.ptr(coef), O.ptr(up), *[O.ptr(x) for x in d], *zp, nlat,
+           *[O.ptr(x) if nlat else None for x in dz], O.stream())
+    torch.cuda.synchronize()
+    return [loss] + d + dz
+
+
+@pytest.mark.parametrize("B,dims,nlat", CAE_CASES)
+def test_plain_and_crit_cae_entry_points_agree(B, dims, nlat):
+    """sp_cae_loss_fwd / _bwd are sp_cae_loss_crit_fwd / _bwd with terms = SP_VLOSS_DICE: the loss, coef[0:8], the four reconstruction
+    gradients and the two latent gradients, bit for bit"""
+    plain_coef, crit_coef = torch.full((8,), float("nan"), device=DEV), torch.full((11,), float("nan"), device=DEV)
+    plain, crit = run_cae(False, B, dims, nlat, plain_coef), run_cae(True, B, dims, nlat, crit_coef)
+    assert bool(torch.isfinite(plain[0])) and all(bool(torch.isfinite(x).all()) for x in plain[1:])
+    assert float(plain[1].abs().max()) > 0 and (nlat == 0 or float(plain[5].abs().max()) > 0)
+    assert torch.equal(plain_coef, crit_coef[:8]) and torch.count_nonzero(crit_coef[8:]) == 0
+    for a, b in zip(plain, crit):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("B,dims,nlat", CAE_CASES)
+def test_plain_cae_entry_points_keep_to_eight_coefficients(B, dims, nlat):
+    """the header promises sp_cae_loss_fwd / _bwd a coef buffer of 8 floats: what lies behind them is neither written by the forward
+    nor read by the backward (a nonzero coef[8] would pick the BCE loop)"""
+    runs = []
+    for sentinel in (0.0, 1.0):
+        buf = torch.full((12,), sentinel, device=DEV)
+        runs.append(run_cae(False, B, dims, nlat, buf[:8]))
+        assert bool((buf[8:] == sentinel).all()), buf
+        assert bool(torch.isfinite(buf[:8]).all())
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+
+
 def test_criteria_modules_against_torch():
     """BCELoss() is torch.nn.BCELoss(); DiceBCELoss(w, b) is BatchDiceLoss(w) + b * torch.nn.BCELoss(): value and gradient"""
     from stroke_prediction_amd.common.metrics import BCELoss, DiceBCELoss

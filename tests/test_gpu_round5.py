@@ -579,7 +579,7 @@ def test_dice_accumulator_clears_itself_between_calls():
         o2 = o.detach().double().requires_grad_(True)
         ref(o2, t).backward()
         assert torch.allclose(o.grad.double(), o2.grad, rtol=1e-4, atol=1e-9)
-    ents = [e for e in M._DICE_SUMS.values()]
+    ents = [e for k, e in M._CRIT_SUMS.items() if k[0] == "dice"]
     assert ents and all(float(e[0].abs().sum()) == 0.0 and not e[1] for e in ents)      # left clean
     for e in ents:                                      # a call that died after sp_dice_sums: sums behind, flag up
         e[0].fill_(3.0)

@@ -52,6 +52,7 @@ def timed(paths, reps, windows, once):
     for n, v in us.items():
         med[n] = statistics.median(v)
         print("%-34s per call: median %8.1f us, min %8.1f, max %8.1f" % (n, med[n], min(v), max(v)))
+        print("%-34s windows: %s" % ("", " ".join("%.1f" % x for x in v)))
     return med
 
 

@@ -50,6 +50,7 @@ def timed(paths, reps, windows, once, bytes_moved):
         med = statistics.median(v)
         print("%-22s per call: median %8.1f us, min %8.1f, max %8.1f   (%.0f MB to move: %.2f TB/s at the median)"
               % (n, med, min(v), max(v), bytes_moved / 1e6, bytes_moved / med / 1e6))
+        print("%-22s windows: %s" % ("", " ".join("%.1f" % x for x in v)))
 
 
 def main():
