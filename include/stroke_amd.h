@@ -46,6 +46,10 @@ enum { SP_VLOSS_DICE = 1, SP_VLOSS_BCE = 2 };
 /* the boundary-loss entry points (sp_bloss_*; one kernel family with sp_vloss_*): the same four columns per channel, the fourth holding
  * sum o*phi */
 #define SP_BLOSS_PITCH(C) SP_VLOSS_PITCH(C)
+/* the class-imbalance entry points (sp_tloss_*; the same kernel family): the terms a call evaluates; the same four columns per channel,
+ * the first three holding FIRST moments (sum o*t, sum o, sum t), the fourth the focal cross-entropy sum */
+enum { SP_TLOSS_TVERSKY = 1, SP_TLOSS_FOCAL = 2 };
+#define SP_TLOSS_PITCH(C) SP_VLOSS_PITCH(C)
 enum { SP_BF16 = 0, SP_F32 = 1,
        /* bf16 PAIR: value = hi + lo with hi = bf16(value) and lo = bf16(value - hi), stored as TWO bf16 tensors of the same
         * shape (the hi tensor is what the bf16 kernels of the backward pass read; the lo tensor lies lo_delta bytes behind it).
@@ -851,6 +855,35 @@ int sp_bloss_finalize_clear(double* sums, const float* w_dice, const float* w_bo
  * (NULL = 1).  No gradient goes to t or phi. */
 int sp_bloss_bwd(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* phi, const float* coef,
                  const float* upstream, int32_t B, int32_t C, int64_t DHW, float* dout, sp_stream_t stream);
+
+/* ------------------------------------------------------------------ class-imbalance criteria: Tversky (Salehi et al. 2017), focal
+ * Tversky (Abraham & Khan 2019) and the focal cross entropy (Lin et al. 2017), alone or added.  The kernel family of sp_vloss_* with
+ * first moments in the three region columns.  With lo = max(log o, -100) and l1 = max(log(1 - o), -100) (torch.nn.BCELoss's
+ * saturation, so o exactly 0 or 1 is legal input):
+ *   fl(o, t)  = -alpha t (1 - o)^gamma lo - (1 - alpha) (1 - t) o^gamma l1
+ *   fl'(o, t) = alpha t [gamma (1 - o)^(gamma-1) lo - (1 - o)^gamma / max(o, 1e-12)]
+ *             + (1 - alpha) (1 - t) [-gamma o^(gamma-1) l1 + o^gamma / max(1 - o, 1e-12)]
+ * focal_gamma is 0 or >= 1 (the gamma x^(gamma-1) terms are absent at 0; 2 is computed with multiplies, any other value as
+ * x^gamma = exp(gamma log x) on the two logarithms), focal_alpha in [0, 1].
+ * sp_tloss_sums: o, t as for sp_dice_sums.  terms: SP_TLOSS_TVERSKY | SP_TLOSS_FOCAL.  sums[row][4*c + k] (fp64, zeroed by the caller;
+ * SP_REDUCE_ROWS replica rows of SP_TLOSS_PITCH(C) doubles) += (sum o*t, sum o, sum t, sum fl) over batch and volume; the columns of a
+ * term that is not asked for are neither computed nor added.  Reduction order and load widths as sp_vloss_sums. */
+int sp_tloss_sums(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, int32_t B, int32_t C, int64_t DHW,
+                  int32_t terms, float focal_gamma, float focal_alpha, double* sums, sp_stream_t stream);
+/* With TP = sum o*t, N = TP + eps, D = TP + fp_weight (sum o - TP) + fn_weight (sum t - TP) + eps and base = 1 - N / D:
+ *   loss = [w_tversky ? sum_c w_c max(base_c, 1e-12)^(1/tversky_gamma) : 0] + [w_focal ? sum_c w4_c F_c / count : 0]
+ * either weight vector ([C], device) may be NULL = the term is absent; tversky_gamma >= 1 (1: the Tversky loss, 4/3: the focal
+ * Tversky loss); count as for sp_vloss_finalize_clear.  coef[3c .. 3c+2] = (ca, c0, c3): d loss / d o = ca*t + c0 + c3*fl'(o, t),
+ * with k = -(w_c / tversky_gamma) base^(1/tversky_gamma - 1) where base >= 1e-12 and 0 where it is not (the gradient of the clamp: a
+ * perfectly predicted or an empty channel has a finite loss and no Tversky gradient),
+ *   ca = k (1/D - N (1 - fp_weight - fn_weight) / D^2),  c0 = -k N fp_weight / D^2,  c3 = w4_c / count.
+ * The replica rows are zeroed again after they are read. */
+int sp_tloss_finalize_clear(double* sums, const float* w_tversky, const float* w_focal, double fp_weight, double fn_weight,
+                            double tversky_gamma, double eps, double count, int32_t C, float* loss, float* coef, sp_stream_t stream);
+/* dout (dense (B, C, DHW)) = *upstream * (ca[c]*t + c0[c] + c3[c]*fl'(o, t)); upstream: device pointer to the scalar gradient
+ * (NULL = 1).  Channels with c3 == 0 skip the logarithms.  Finite for every o in [0, 1]. */
+int sp_tloss_bwd(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* coef, const float* upstream,
+                 float focal_gamma, float focal_alpha, int32_t B, int32_t C, int64_t DHW, float* dout, sp_stream_t stream);
 
 /* ------------------------------------------------------------------ fused classify head (Unet3D.py:49-54,75-77)
  * seg = sigmoid(W2 * lrelu(W1*x + b1) + b2): x channels-last [B*nvox][CP], seg NCDHW fp32 [B][NC][nvox].

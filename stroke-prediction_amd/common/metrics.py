@@ -17,8 +17,14 @@ Euclidean distance map of the label, alone or added to Dice with a weight that c
 and channel on the device (``sp_signed_distance_batch``) and run on ``sp_bloss_sums`` / ``_finalize_clear`` / ``_bwd``; they take the
 ``mean_of_channel_losses`` route, and the CAE learners compose them literally.
 
-All five criteria are ONE autograd function, ``_CriterionFn``, driven by a record per kernel family (``_FAMILIES``: ``sp_dice_*``,
-``sp_vloss_*``, ``sp_bloss_*``), with one registry of accumulators, ``_CRIT_SUMS``.
+``TverskyLoss`` (Salehi et al., MLMI 2017; with ``gamma = 4/3`` the focal Tversky loss of Abraham & Khan, ISBI 2019), ``FocalBCELoss``
+(the focal cross entropy of Lin et al., ICCV 2017) and ``TverskyFocalBCELoss``, their sum -- the criteria for lesions that fill a
+fraction of a percent of a patch: false negatives weighed against false positives, easy background voxels down-weighted -- run on
+``sp_tloss_sums`` / ``_finalize_clear`` / ``_bwd``; they take the ``mean_of_channel_losses`` route, and the CAE learners compose them
+literally.
+
+All eight criteria are ONE autograd function, ``_CriterionFn``, driven by a record per kernel family (``_FAMILIES``: ``sp_dice_*``,
+``sp_vloss_*``, ``sp_bloss_*``, ``sp_tloss_*``), with one registry of accumulators, ``_CRIT_SUMS``.
 """
 import collections
 
@@ -84,11 +90,13 @@ def batch_mean(t):
     return torch.mean(t)
 
 
-_Family = collections.namedtuple("_Family", "sums finalize bwd pitch ncoef select fourth phi")
+_Family = collections.namedtuple("_Family", "sums finalize bwd pitch ncoef select fourth phi sums_scalars finalize_scalars bwd_scalars",
+                                 defaults=(lambda extra: (),) * 3)
 # The kernel families of the per-channel criteria, one record each: the three entry points; the accumulator's row pitch (doubles) for C
 # channels; the coefficients per channel; ``select``: the integer the sums call takes behind DHW; ``fourth``: there is a fourth moment --
 # finalize takes a second weight vector and the element count; ``phi``: the signed-distance map of the targets is a third operand of
-# sums and backward, and finalize takes the device scalar that scales the fourth moment's weights.
+# sums and backward, and finalize takes the device scalar that scales the fourth moment's weights; ``*_scalars``: the host scalars a
+# call takes out of the criterion's ``extra`` tuple -- sums behind ``select``, finalize in front of eps, backward behind upstream.
 _FAMILIES = {
     "dice": _Family("sp_dice_sums", "sp_dice_finalize_clear", "sp_dice_bwd", lambda L, C: (3 * C + 15) // 16 * 16, 2,
                     lambda L, w_dice, w4: (), False, False),
@@ -97,6 +105,10 @@ _FAMILIES = {
                      True, False),
     "bloss": _Family("sp_bloss_sums", "sp_bloss_finalize_clear", "sp_bloss_bwd", lambda L, C: L.SP_BLOSS_PITCH(C), 3,
                      lambda L, w_dice, w4: (0 if w_dice is None else 1,), True, True),
+    # extra = (fp_weight, fn_weight, tversky_gamma, focal_gamma, focal_alpha); w_dice: the Tversky weights, w4: the focal ones
+    "tloss": _Family("sp_tloss_sums", "sp_tloss_finalize_clear", "sp_tloss_bwd", lambda L, C: L.SP_TLOSS_PITCH(C), 3,
+                     lambda L, w_dice, w4: ((L.SP_TLOSS_TVERSKY if w_dice is not None else 0) | (L.SP_TLOSS_FOCAL if w4 is not None else 0),),
+                     True, False, lambda extra: extra[3:5], lambda extra: extra[0:3], lambda extra: extra[3:5]),
 }
 _CRIT_SUMS = {}      # (family, device, C, stream) -> [replica rows of that family's sums (zero between calls), busy]
 
@@ -105,13 +117,15 @@ class _CriterionFn(torch.autograd.Function):
     """loss = [1 - sum_c wd_c (2 I_c + eps) / (O_c + T_c + eps)] + [sum_c w4_c * scale * mean_c X], either bracket absent when its
     weights are None; sums and means over batch and volume per channel.  ``family`` names the kernels: "dice" (the first bracket only),
     "vloss" (X = bce(o, t) with torch.nn.BCELoss semantics) or "bloss" (X = o * phi, phi = signed_distance_batch(targets), scale a
-    one-float device tensor read by the finalize kernel: a captured step follows its schedule).  Two HIP launches forward (sums,
+    one-float device tensor read by the finalize kernel: a captured step follows its schedule).  Family "tloss" has other brackets:
+    [sum_c wd_c max(1 - TI_c, 1e-12)^(1/tversky_gamma)] + [sum_c w4_c mean_c fl(o, t)], TI the Tversky index on first moments and fl the
+    focal cross entropy, their scalars in ``extra`` = (fp_weight, fn_weight, tversky_gamma, focal_gamma, focal_alpha).  Two HIP launches forward (sums,
     finalize) behind the signed-distance ones, and one backward; the scalar algebra never leaves the device.  In the exact
     data-parallel mode the sums are all-reduced and the element count is the global one: the local backward yields this rank's share
     of the whole-batch gradient (as _GlobalMeanFn); phi is local."""
 
     @staticmethod
-    def forward(ctx, family, outputs, targets, w_dice, w4, scale, eps):
+    def forward(ctx, family, outputs, targets, w_dice, w4, scale, eps, extra):
         from stroke_prediction_amd.runtime import lib as L, ops as O
         from stroke_prediction_amd.runtime.layers import SYNC, _allreduce
         fam = _FAMILIES[family]
@@ -128,7 +142,8 @@ class _CriterionFn(torch.autograd.Function):
             ent = _CRIT_SUMS[key] = [torch.zeros(L.SP_REDUCE_ROWS, fam.pitch(L, C), dtype=torch.float64, device=o.device), False]
         sums = ent[0]   # replica rows
         ent[1] = True
-        L.call(fam.sums, O.ptr(o), obs, O.ptr(t), tbs, *[O.ptr(p) for p in phi], B, C, dhw, *fam.select(L, w_dice, w4), O.ptr(sums), O.stream())
+        L.call(fam.sums, O.ptr(o), obs, O.ptr(t), tbs, *[O.ptr(p) for p in phi], B, C, dhw, *fam.select(L, w_dice, w4), *fam.sums_scalars(extra),
+               O.ptr(sums), O.stream())
         count = float(B * dhw)
         if SYNC["on"]:                  # ratios and means of WHOLE-batch sums (metrics.py:24-27): make them global
             _allreduce(sums)
@@ -137,11 +152,11 @@ class _CriterionFn(torch.autograd.Function):
         ws = [None if w is None else O.ptr(_weights_on(o.device, w)) for w in ((w_dice, w4) if fam.fourth else (w_dice,))]
         loss = torch.empty((), dtype=torch.float32, device=o.device)
         coef = torch.empty(fam.ncoef * C, dtype=torch.float32, device=o.device)
-        L.call(fam.finalize, O.ptr(sums), *ws, *([O.ptr(scale)] if fam.phi else []), float(eps), *([count] if fam.fourth else []), C,
-               O.ptr(loss), O.ptr(coef), O.stream())
+        L.call(fam.finalize, O.ptr(sums), *ws, *([O.ptr(scale)] if fam.phi else []), *fam.finalize_scalars(extra), float(eps),
+               *([count] if fam.fourth else []), C, O.ptr(loss), O.ptr(coef), O.stream())
         ent[1] = False
         ctx.save_for_backward(o, t, *phi, coef)
-        ctx.family, ctx.strides = family, (obs, tbs)
+        ctx.family, ctx.strides, ctx.extra = family, (obs, tbs), extra
         return loss
 
     @staticmethod
@@ -152,9 +167,10 @@ class _CriterionFn(torch.autograd.Function):
         B, C = o.shape[0], o.shape[1]
         up = gloss if (gloss.dtype == torch.float32 and gloss.is_contiguous()) else gloss.float().contiguous()
         d = torch.empty(o.shape, dtype=torch.float32, device=o.device)
-        L.call(_FAMILIES[ctx.family].bwd, O.ptr(o), obs, O.ptr(t), tbs, *[O.ptr(p) for p in phi], O.ptr(coef), O.ptr(up), B, C,
+        fam = _FAMILIES[ctx.family]
+        L.call(fam.bwd, O.ptr(o), obs, O.ptr(t), tbs, *[O.ptr(p) for p in phi], O.ptr(coef), O.ptr(up), *fam.bwd_scalars(ctx.extra), B, C,
                o.numel() // (B * C), O.ptr(d), O.stream())
-        return None, d, None, None, None, None, None
+        return None, d, None, None, None, None, None, None
 
 
 class BatchDiceLoss(LossModule):
@@ -171,7 +187,7 @@ class BatchDiceLoss(LossModule):
         assert outputs.shape == targets.shape
         if not outputs.is_cuda or self._dim != 1:
             raise RuntimeError("BatchDiceLoss (stroke_prediction_amd) runs on the GPU with channel dim 1 only")
-        return _CriterionFn.apply("dice", outputs, targets, tuple(float(w) for w in self._label_weights), None, None, float(self._epsilon))
+        return _CriterionFn.apply("dice", outputs, targets, tuple(float(w) for w in self._label_weights), None, None, float(self._epsilon), None)
 
 
 def _check_voxel_loss_inputs(name, outputs, targets, label_weights):
@@ -198,7 +214,7 @@ class BCELoss(LossModule):
 
     def forward(self, outputs, targets):
         _check_voxel_loss_inputs("BCELoss", outputs, targets, self._label_weights)
-        return _CriterionFn.apply("vloss", outputs, targets, None, self.weights(outputs.shape[1]), None, 0.0)
+        return _CriterionFn.apply("vloss", outputs, targets, None, self.weights(outputs.shape[1]), None, 0.0, None)
 
 
 class DiceBCELoss(LossModule):
@@ -215,7 +231,7 @@ class DiceBCELoss(LossModule):
         _check_voxel_loss_inputs("DiceBCELoss", outputs, targets, self._label_weights)
         C = outputs.shape[1]
         return _CriterionFn.apply("vloss", outputs, targets, tuple(float(w) for w in self._label_weights),
-                                  (float(self._bce_weight) / C,) * C, None, float(self._epsilon))
+                                  (float(self._bce_weight) / C,) * C, None, float(self._epsilon), None)
 
 
 def signed_distance_workspace_floats(B, C, D, H, W):
@@ -298,7 +314,7 @@ class BoundaryLoss(LossModule, _ScheduledBoundaryWeight):
 
     def forward(self, outputs, targets):
         _check_voxel_loss_inputs("BoundaryLoss", outputs, targets, self._label_weights)
-        return _CriterionFn.apply("bloss", outputs, targets, None, self.weights(outputs.shape[1]), self._scale_on(outputs.device), 0.0)
+        return _CriterionFn.apply("bloss", outputs, targets, None, self.weights(outputs.shape[1]), self._scale_on(outputs.device), 0.0, None)
 
 
 class DiceBoundaryLoss(LossModule, _ScheduledBoundaryWeight):
@@ -316,7 +332,124 @@ class DiceBoundaryLoss(LossModule, _ScheduledBoundaryWeight):
         _check_voxel_loss_inputs("DiceBoundaryLoss", outputs, targets, self._label_weights)
         C = outputs.shape[1]
         return _CriterionFn.apply("bloss", outputs, targets, tuple(float(w) for w in self._label_weights), (1.0 / C,) * C,
-                                  self._scale_on(outputs.device), float(self._epsilon))
+                                  self._scale_on(outputs.device), float(self._epsilon), None)
+
+
+def _check_tversky(name, fp_weight, fn_weight, gamma):
+    if not (fp_weight >= 0.0 and fn_weight >= 0.0):
+        raise ValueError("%s: fp_weight and fn_weight are at least 0 (got %r, %r)" % (name, fp_weight, fn_weight))
+    if not gamma >= 1.0:
+        raise ValueError("%s: the Tversky gamma is at least 1 (got %r)" % (name, gamma))
+
+
+def _check_focal(name, gamma, alpha):
+    if not (gamma == 0.0 or gamma >= 1.0):
+        raise ValueError("%s: the focal gamma is 0 or at least 1 (got %r)" % (name, gamma))
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("%s: alpha lies in [0, 1] (got %r)" % (name, alpha))
+
+
+class TverskyLoss(LossModule):
+    """``sum_c w_c (1 - TI_c)^(1/gamma)`` on (B, C, ...) GPU tensors (channel dim 1), TI = (TP + eps) / (TP + fp_weight FP +
+    fn_weight FN + eps) with the soft counts TP = sum o t, FP = sum o (1 - t), FN = sum (1 - o) t over batch and volume.  fp_weight =
+    fn_weight = 0.5 is the Dice index on first moments; fn_weight > fp_weight favours recall.  ``gamma = 4/3`` is the focal Tversky loss.
+    A channel with TI = 1 (a perfect or an empty one) has a finite loss and no gradient."""
+
+    def __init__(self, label_weights, fp_weight=0.3, fn_weight=0.7, gamma=1.0, epsilon=0.0000001):
+        super(TverskyLoss, self).__init__()
+        self._label_weights = label_weights
+        self._fp_weight = fp_weight
+        self._fn_weight = fn_weight
+        self._gamma = gamma
+        self._epsilon = epsilon
+        self._dim = 1
+        self.check()
+
+    def check(self):
+        _check_tversky("TverskyLoss", self._fp_weight, self._fn_weight, self._gamma)
+
+    def extra(self):
+        return float(self._fp_weight), float(self._fn_weight), float(self._gamma), 2.0, 0.25      # (no focal term: its scalars are not read)
+
+    def forward(self, outputs, targets):
+        _check_voxel_loss_inputs("TverskyLoss", outputs, targets, self._label_weights)
+        return _CriterionFn.apply("tloss", outputs, targets, tuple(float(w) for w in self._label_weights), None, None, float(self._epsilon),
+                                  self.extra())
+
+
+class FocalBCELoss(LossModule):
+    """``sum_c w_c mean_c fl(o, t)``, fl = -alpha t (1 - o)^gamma log o - (1 - alpha) (1 - t) o^gamma log(1 - o) with the logarithms
+    clamped at -100 as ``torch.nn.BCELoss`` clamps them, on (B, C, ...) GPU tensors (channel dim 1).  The default weights, 1 / C each, are
+    the mean over everything; ``gamma = 0, alpha = 0.5`` is half of ``BCELoss()``.  gamma is 0 or at least 1."""
+
+    def __init__(self, label_weights=None, gamma=2.0, alpha=0.25):
+        super(FocalBCELoss, self).__init__()
+        self._label_weights = label_weights
+        self._gamma = gamma
+        self._alpha = alpha
+        self._dim = 1
+        self.check()
+
+    def check(self):
+        _check_focal("FocalBCELoss", self._gamma, self._alpha)
+
+    def weights(self, C):
+        if self._label_weights is None:
+            return (1.0 / C,) * C
+        return tuple(float(w) for w in self._label_weights)
+
+    def extra(self):
+        return 0.0, 0.0, 1.0, float(self._gamma), float(self._alpha)
+
+    def forward(self, outputs, targets):
+        _check_voxel_loss_inputs("FocalBCELoss", outputs, targets, self._label_weights)
+        return _CriterionFn.apply("tloss", outputs, targets, None, self.weights(outputs.shape[1]), None, 0.0, self.extra())
+
+
+class TverskyFocalBCELoss(LossModule):
+    """``TverskyLoss(label_weights, fp_weight, fn_weight, tversky_gamma, epsilon)(o, t) + focal_weight * FocalBCELoss(None, focal_gamma,
+    focal_alpha)(o, t)`` in one sums / finalize / backward set."""
+
+    def __init__(self, label_weights, focal_weight=1.0, fp_weight=0.3, fn_weight=0.7, tversky_gamma=1.0, focal_gamma=2.0, focal_alpha=0.25,
+                 epsilon=0.0000001):
+        super(TverskyFocalBCELoss, self).__init__()
+        self._label_weights = label_weights
+        self._focal_weight = focal_weight
+        self._fp_weight = fp_weight
+        self._fn_weight = fn_weight
+        self._tversky_gamma = tversky_gamma
+        self._focal_gamma = focal_gamma
+        self._focal_alpha = focal_alpha
+        self._epsilon = epsilon
+        self._dim = 1
+        self.check()
+
+    def check(self):
+        _check_tversky("TverskyFocalBCELoss", self._fp_weight, self._fn_weight, self._tversky_gamma)
+        _check_focal("TverskyFocalBCELoss", self._focal_gamma, self._focal_alpha)
+
+    def extra(self):
+        return float(self._fp_weight), float(self._fn_weight), float(self._tversky_gamma), float(self._focal_gamma), float(self._focal_alpha)
+
+    def forward(self, outputs, targets):
+        _check_voxel_loss_inputs("TverskyFocalBCELoss", outputs, targets, self._label_weights)
+        C = outputs.shape[1]
+        return _CriterionFn.apply("tloss", outputs, targets, tuple(float(w) for w in self._label_weights),
+                                  (float(self._focal_weight) / C,) * C, None, float(self._epsilon), self.extra())
+
+
+def _single_label_imbalance_terms(criterion):
+    """(Tversky weight or None, focal weight or None, eps, extra) of a TverskyLoss / FocalBCELoss / TverskyFocalBCELoss that weighs ONE
+    label class -- what ``mean_of_channel_losses`` evaluates per channel --, or None for anything else."""
+    if getattr(criterion, "_dim", None) != 1:
+        return None
+    if isinstance(criterion, TverskyLoss) and len(criterion._label_weights) == 1:
+        return float(criterion._label_weights[0]), None, float(criterion._epsilon), criterion.extra()
+    if isinstance(criterion, FocalBCELoss) and (criterion._label_weights is None or len(criterion._label_weights) == 1):
+        return None, criterion.weights(1)[0], 0.0, criterion.extra()
+    if isinstance(criterion, TverskyFocalBCELoss) and len(criterion._label_weights) == 1:
+        return float(criterion._label_weights[0]), float(criterion._focal_weight), float(criterion._epsilon), criterion.extra()
+    return None
 
 
 def _single_label_boundary_terms(criterion):
@@ -347,7 +480,9 @@ def _single_label_terms(criterion):
 
 def make_criterion(name):
     """The training scripts' ``--criterion``: ``dice`` (the reference's choice), ``bce`` (the one its comment names), ``dicebce``,
-    ``boundary`` (the signed-distance loss) and ``diceboundary`` (Dice + boundary weight * boundary loss)."""
+    ``boundary`` (the signed-distance loss), ``diceboundary`` (Dice + boundary weight * boundary loss) and the class-imbalance
+    criteria ``tversky``, ``focaltversky`` (Tversky with gamma 4/3), ``focalbce`` and ``tverskyfocalbce`` (Tversky + focal weight * focal
+    cross entropy)."""
     if name == "dice":
         return BatchDiceLoss([1.0])
     if name == "bce":
@@ -358,14 +493,32 @@ def make_criterion(name):
         return BoundaryLoss()
     if name == "diceboundary":
         return DiceBoundaryLoss([1.0])
-    raise ValueError("criterion %r: one of dice, bce, dicebce, boundary, diceboundary" % (name,))
+    if name == "tversky":
+        return TverskyLoss([1.0])
+    if name == "focaltversky":
+        return TverskyLoss([1.0], gamma=4.0 / 3.0)
+    if name == "focalbce":
+        return FocalBCELoss()
+    if name == "tverskyfocalbce":
+        return TverskyFocalBCELoss([1.0])
+    raise ValueError("criterion %r: one of dice, bce, dicebce, boundary, diceboundary, tversky, focaltversky, focalbce, tverskyfocalbce" % (name,))
 
 
 def configure_criterion(criterion, args):
-    """Apply the training scripts' ``--boundaryweight`` / ``--boundaryramp`` to a criterion that has a boundary term; any other
-    criterion is returned as it is."""
+    """Apply the training scripts' ``--boundaryweight`` / ``--boundaryramp`` to a criterion that has a boundary term, and
+    ``--tverskyfp`` / ``--tverskyfn`` / ``--tverskygamma`` / ``--focalgamma`` / ``--focalalpha`` / ``--focalweight`` (None = the
+    criterion's own value) to one that has the matching term; any other criterion is returned as it is."""
     if isinstance(criterion, (BoundaryLoss, DiceBoundaryLoss)):
         criterion.set_boundary_schedule(getattr(args, "boundaryweight", criterion.boundary_weight()), getattr(args, "boundaryramp", 0.0))
+    fields = {TverskyLoss: dict(tverskyfp="_fp_weight", tverskyfn="_fn_weight", tverskygamma="_gamma"),
+              FocalBCELoss: dict(focalgamma="_gamma", focalalpha="_alpha"),
+              TverskyFocalBCELoss: dict(tverskyfp="_fp_weight", tverskyfn="_fn_weight", tverskygamma="_tversky_gamma", focalgamma="_focal_gamma",
+                                        focalalpha="_focal_alpha", focalweight="_focal_weight")}.get(type(criterion))
+    if fields is not None:
+        for flag, field in fields.items():
+            if getattr(args, flag, None) is not None:
+                setattr(criterion, field, float(getattr(args, flag)))
+        criterion.check()
     return criterion
 
 
@@ -460,10 +613,14 @@ def mean_of_channel_losses(criterion, outputs, targets):
     launch on the base tensors, and the gradient lands on the segmentation directly (no slice-backward zero-fill,
     copy and add per channel).  A single-label BCELoss (weights 1/n) or DiceBCELoss (Dice weights w/n, BCE weights
     bce_weight/n) takes the same route on the sp_vloss_* kernels, a single-label BoundaryLoss / DiceBoundaryLoss on
-    sp_signed_distance_batch and the sp_bloss_* kernels (one signed-distance set for all n channels).  Anything else: the literal
+    sp_signed_distance_batch and the sp_bloss_* kernels (one signed-distance set for all n channels), a single-label TverskyLoss /
+    FocalBCELoss / TverskyFocalBCELoss on the sp_tloss_* kernels (Tversky weights w/n, focal weights w/n).  Anything else: the literal
     sum of calls."""
     n = len(outputs)
-    family, terms = "bloss", _single_label_boundary_terms(criterion)
+    family, terms, extra = "bloss", _single_label_boundary_terms(criterion), None
+    imbalance = _single_label_imbalance_terms(criterion)
+    if imbalance is not None:
+        family, terms, extra = "tloss", imbalance[:3], imbalance[3]
     if terms is None:
         terms = _single_label_terms(criterion)
         family = "dice" if terms is not None and terms[1] is None else "vloss"
@@ -472,7 +629,7 @@ def mean_of_channel_losses(criterion, outputs, targets):
         if ob is not None and tb is not None:
             w_dice, w4, eps = terms
             return _CriterionFn.apply(family, ob, tb, None if w_dice is None else (w_dice / n,) * n, None if w4 is None else (w4 / n,) * n,
-                                      criterion._scale_on(ob.device) if family == "bloss" else None, eps)
+                                      criterion._scale_on(ob.device) if family == "bloss" else None, eps, extra)
     total = criterion(outputs[0], targets[0])
     for o, t in zip(outputs[1:], targets[1:]):
         total = total + criterion(o, t)

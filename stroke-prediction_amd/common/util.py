@@ -31,15 +31,31 @@ _EXPERIMENT = [
     ("--devicecache", dict(action="store_true", default=False,
                            help="(MI355X build) upload every case once and gather each batch from the device-resident cache with one "
                                 "kernel launch (data.DeviceCaseCache / CachedBatchLoader)")),
-    ("--criterion", dict(type=str, default="dice", choices=["dice", "bce", "dicebce", "boundary", "diceboundary"],
+    ("--criterion", dict(type=str, default="dice", choices=["dice", "bce", "dicebce", "boundary", "diceboundary", "tversky", "focaltversky", "focalbce",
+                                                                  "tverskyfocalbce"],
                          help="(MI355X build) training criterion (metrics.make_criterion): BatchDiceLoss([1.0]) as the reference, the "
                               "nn.BCELoss() its scripts name as the alternative, their sum, the boundary (signed-distance) loss "
-                              "mean(o * phi(t)), or Dice + boundary weight * boundary loss")),
+                              "mean(o * phi(t)), Dice + boundary weight * boundary loss, or the class-imbalance criteria: the Tversky "
+                              "loss, the focal Tversky loss (gamma 4/3), the focal cross entropy, or Tversky + focal weight * focal "
+                              "cross entropy")),
     ("--boundaryweight", dict(type=float, default=0.01,
                               help="(MI355X build) --criterion boundary / diceboundary: weight of the boundary term at epoch 0")),
     ("--boundaryramp", dict(type=float, default=0.0,
                             help="(MI355X build) --criterion boundary / diceboundary: the weight grows by this much per epoch, capped at "
                                  "1.0 (Kervadec et al. use 0.01)")),
+    ("--tverskyfp", dict(type=float, default=None,
+                         help="(MI355X build) --criterion tversky / focaltversky / tverskyfocalbce: weight of the false positives (default 0.3)")),
+    ("--tverskyfn", dict(type=float, default=None,
+                         help="(MI355X build) --criterion tversky / focaltversky / tverskyfocalbce: weight of the false negatives (default 0.7)")),
+    ("--tverskygamma", dict(type=float, default=None,
+                            help="(MI355X build) --criterion tversky / focaltversky / tverskyfocalbce: the loss is (1 - TI)^(1/gamma), gamma >= 1 "
+                                 "(default 1, focaltversky 4/3)")),
+    ("--focalgamma", dict(type=float, default=None,
+                          help="(MI355X build) --criterion focalbce / tverskyfocalbce: the focusing exponent, 0 or >= 1 (default 2)")),
+    ("--focalalpha", dict(type=float, default=None,
+                          help="(MI355X build) --criterion focalbce / tverskyfocalbce: weight of the foreground voxels in [0, 1] (default 0.25)")),
+    ("--focalweight", dict(type=float, default=None,
+                           help="(MI355X build) --criterion tverskyfocalbce: weight of the focal cross entropy beside the Tversky term (default 1)")),
 ]
 _CAE = [
     ("--epochs", dict(type=int, default=300, help="Number of epochs")),

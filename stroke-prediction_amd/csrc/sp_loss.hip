@@ -1,6 +1,7 @@
 // The training criteria (include/stroke_amd.h), each as sums -> finalize -> backward with the scalar algebra on the device:
 //   * sp_dice_*: BatchDiceLoss (metrics.py:16-28), three moments per channel -- the headline training step's path;
-//   * sp_vloss_* / sp_bloss_*: ONE per-channel family of four moments, the fourth holding nothing, sum bce or sum o*phi;
+//   * sp_vloss_* / sp_bloss_* / sp_tloss_*: ONE per-channel family of four moments, the three region columns holding second or first
+//     moments, the fourth nothing, sum bce, sum o*phi or the focal cross-entropy sum;
 //   * sp_cae_loss_* / sp_cae_loss_crit_*: the CAE reconstruction loss (CaeReconstructionLearner.py:52-70), ONE kernel set.
 // Every sums kernel reduces alike: per-thread fp32, wave sum, the four waves in order (sp_cols_sum), one fp64 atomic per workgroup and
 // column into a replica row.  All of it is bandwidth- or latency-bound elementwise work on fp32; nothing here depends on the 16-bit
@@ -115,28 +116,65 @@ extern "C" int sp_dice_bwd(const float* o, int64_t o_bstride, const float* t, in
 // sums[c] = (sum o*t, sum o*o, sum t*t, X) over batch and volume, the first three present with DICE, X chosen by X4: nothing, sum bce
 // (sp_vloss_*: torch.nn.BCELoss semantics, finite at a saturated sigmoid, o = 0 or 1) or sum o*phi (sp_bloss_*: phi a third input,
 // dense (B, C, DHW)).  d loss / d o = ca*t + cb*o + c3*X'.
-enum { X4_NONE = 0, X4_BCE = 1, X4_PHI = 2 };
+// FIRST (sp_tloss_*: Tversky and focal criteria): the region columns hold first moments, (sum o*t, sum o, sum t), X is the focal cross
+// entropy sum fl(o, t) and d loss / d o = ca*t + cb + c3*fl'.  The focal exponent: X4_FOCAL2 is gamma == 2 at compile time (the default
+// of the criteria: multiplies only); X4_FOCAL reads gamma from the arguments and branches, uniformly over the launch, between 0, 1
+// (multiplies again) and the general x^gamma = expf(gamma log x) on the two logarithms the term has anyway.
+enum { X4_NONE = 0, X4_BCE = 1, X4_PHI = 2, X4_FOCAL2 = 3, X4_FOCAL = 4 };
 __device__ __forceinline__ float bce_term(float o, float t) {
   return -(t * fmaxf(logf(o), -100.f) + (1.f - t) * fmaxf(logf(1.f - o), -100.f));
 }
 // d bce / d o: (o - t) / max(o (1 - o), 1e-12)
 __device__ __forceinline__ float bce_grad(float o, float t) { return (o - t) / fmaxf(o * (1.f - o), 1e-12f); }
-template <bool DICE, int X4> __device__ __forceinline__ void crit_acc(float a, float b, float p, float (&s)[4]) {
-  if (DICE) { s[0] += a * b; s[1] += a * a; s[2] += b * b; }
+// fl(o, t) = -al t (1 - o)^g lo - (1 - al) (1 - t) o^g l1 with the logarithms clamped as bce_term clamps them: o = 0 and o = 1 give
+// finite values (the clamped logarithm stands in the exponent too: 0^g = expf(-100 g), 1 at g = 0 as pow has it)
+template <int X4> __device__ __forceinline__ float focal_term(float o, float t, float g, float al) {
+  const float q = 1.f - o, lo = fmaxf(logf(o), -100.f), l1 = fmaxf(logf(q), -100.f);
+  float pq, po;
+  if (X4 == X4_FOCAL2) { pq = q * q; po = o * o; }
+  else if (g == 0.f) { pq = 1.f; po = 1.f; }
+  else if (g == 1.f) { pq = q; po = o; }
+  else { pq = expf(g * l1); po = expf(g * lo); }
+  return -(al * t * pq * lo) - (1.f - al) * (1.f - t) * po * l1;
+}
+// d fl / d o = al t [g (1 - o)^(g-1) lo - (1 - o)^g / max(o, 1e-12)] + (1 - al) (1 - t) [-g o^(g-1) l1 + o^g / max(1 - o, 1e-12)]; the
+// g x^(g-1) terms are absent at g = 0.  x^g = x * x^(g-1): two expf for a general g.  Finite for every o in [0, 1].
+template <int X4> __device__ __forceinline__ float focal_grad(float o, float t, float g, float al) {
+  const float q = 1.f - o, lo = fmaxf(logf(o), -100.f), l1 = fmaxf(logf(q), -100.f);
+  const float ro = 1.f / fmaxf(o, 1e-12f), rq = 1.f / fmaxf(q, 1e-12f);
+  float A, Bq;      // the bracket of the t = 1 side / of the t = 0 side
+  if (X4 == X4_FOCAL2) { A = 2.f * q * lo - q * q * ro; Bq = o * o * rq - 2.f * o * l1; }
+  else if (g == 0.f) { A = -ro; Bq = rq; }
+  else if (g == 1.f) { A = lo - q * ro; Bq = o * rq - l1; }
+  else {
+    const float pq = expf((g - 1.f) * l1), po = expf((g - 1.f) * lo);      // (1 - o)^(g-1), o^(g-1)
+    A = g * pq * lo - pq * q * ro; Bq = po * o * rq - g * po * l1;
+  }
+  return al * t * A + (1.f - al) * (1.f - t) * Bq;
+}
+template <bool DICE, int X4, bool FIRST = false>
+__device__ __forceinline__ void crit_acc(float a, float b, float p, float (&s)[4], float fg = 0.f, float fa = 0.f) {
+  if (DICE && !FIRST) { s[0] += a * b; s[1] += a * a; s[2] += b * b; }
+  if (DICE && FIRST) { s[0] += a * b; s[1] += a; s[2] += b; }
   if (X4 == X4_BCE) s[3] += bce_term(a, b);
   if (X4 == X4_PHI) s[3] += a * p;
+  if (X4 == X4_FOCAL2 || X4 == X4_FOCAL) s[3] += focal_term<X4>(a, b, fg, fa);
 }
-template <int X4> __device__ __forceinline__ float crit_grad(float a, float b, float p, float ca, float cb, float c3) {
-  const float g = ca * b + cb * a;
+template <int X4, bool FIRST = false>
+__device__ __forceinline__ float crit_grad(float a, float b, float p, float ca, float cb, float c3, float fg = 0.f, float fa = 0.f) {
+  const float g = FIRST ? ca * b + cb : ca * b + cb * a;
+  if (X4 == X4_FOCAL2 || X4 == X4_FOCAL) return g + c3 * focal_grad<X4>(a, b, fg, fa);
   return X4 == X4_BCE ? g + c3 * bce_grad(a, b) : (X4 == X4_PHI ? g + c3 * p : g);
 }
 // The layout and the reduction order of dice_sums_kernel; an operand no moment needs (t without DICE and BCE, phi without X4_PHI) is
 // not loaded, a column whose term is absent is neither reduced nor added.
 // VEC: DHW % 4 == 0 and every row base 16-byte aligned (checked by the launcher) -> one 16-byte load per lane and operand.
-template <bool DICE, int X4, bool VEC>
+// FIRST: first moments in the region columns; fg / fa: the focal exponent and alpha (read by the focal instances only).
+template <bool DICE, int X4, bool VEC, bool FIRST = false>
 __global__ __launch_bounds__(256) void crit_sums_kernel(const float* __restrict__ o, int64_t obs, const float* __restrict__ t, int64_t tbs,
-                                                        const float* __restrict__ phi, int C, int64_t DHW, double* __restrict__ sums) {
-  constexpr bool T = DICE || X4 == X4_BCE, PHI = X4 == X4_PHI;
+                                                        const float* __restrict__ phi, int C, int64_t DHW, double* __restrict__ sums,
+                                                        float fg, float fa) {
+  constexpr bool T = DICE || X4 == X4_BCE || X4 == X4_FOCAL2 || X4 == X4_FOCAL, PHI = X4 == X4_PHI;
   // grid.y = b*C + c ; grid.x strides over the volume
   const int bc = blockIdx.y, c = bc % C, b = bc / C;
   const float* op = o + (int64_t)b * obs + (int64_t)c * DHW;
@@ -153,11 +191,12 @@ __global__ __launch_bounds__(256) void crit_sums_kernel(const float* __restrict_
       float4 bb = make_float4(0.f, 0.f, 0.f, 0.f), p = bb;
       if (PHI) p = p4[i];
       if (T) bb = t4[i];
-      crit_acc<DICE, X4>(a.x, bb.x, p.x, s); crit_acc<DICE, X4>(a.y, bb.y, p.y, s); crit_acc<DICE, X4>(a.z, bb.z, p.z, s); crit_acc<DICE, X4>(a.w, bb.w, p.w, s);
+      crit_acc<DICE, X4, FIRST>(a.x, bb.x, p.x, s, fg, fa); crit_acc<DICE, X4, FIRST>(a.y, bb.y, p.y, s, fg, fa);
+      crit_acc<DICE, X4, FIRST>(a.z, bb.z, p.z, s, fg, fa); crit_acc<DICE, X4, FIRST>(a.w, bb.w, p.w, s, fg, fa);
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < DHW; i += (int64_t)gridDim.x * 256)
-      crit_acc<DICE, X4>(op[i], T ? tp[i] : 0.f, PHI ? pp[i] : 0.f, s);
+      crit_acc<DICE, X4, FIRST>(op[i], T ? tp[i] : 0.f, PHI ? pp[i] : 0.f, s, fg, fa);
   }
   __shared__ float red[4 * 4];      // [wave][moment], added up in wave order (sp_cols_sum)
 #pragma unroll
@@ -176,20 +215,25 @@ static inline bool crit_vec_ok(const void* p, int64_t bstride, int B, int64_t DH
 static inline bool crit_args_ok(const float* o, int64_t obs, const float* t, int64_t tbs, int32_t B, int32_t C, int64_t DHW) {
   return o && t && B >= 1 && C >= 1 && DHW >= 1 && (int64_t)B * C <= 65535 && obs >= C * DHW && tbs >= C * DHW;
 }
-// phi != NULL: the fourth moment is sum o*phi, and phi takes part in the choice of the load width
+// phi != NULL: the fourth moment is sum o*phi, and phi takes part in the choice of the load width; first: first moments (sp_tloss_*)
 static void crit_sums_launch(const float* o, int64_t obs, const float* t, int64_t tbs, const float* phi, int32_t B, int32_t C, int64_t DHW,
-                             bool dice, int x4, double* sums, sp_stream_t stream) {
+                             bool dice, int x4, double* sums, sp_stream_t stream, bool first = false, float fg = 0.f, float fa = 0.f) {
   int64_t gx = (DHW + 256 * 8 - 1) / (256 * 8);
   if (gx > 256) gx = 256;
   const bool vec = crit_vec_ok(o, obs, B, DHW) && crit_vec_ok(t, tbs, B, DHW) && (!phi || crit_vec_ok(phi, 0, 1, DHW));
-#define SP_CRIT_SUMS(D_, X_)                                                                                                            \
+#define SP_CRIT_SUMS(D_, X_, F_)                                                                                                        \
   do {                                                                                                                                  \
-    if (vec) hipLaunchKernelGGL((crit_sums_kernel<D_, X_, true>), dim3((unsigned)gx, B * C), dim3(256), 0, ST(stream), o, obs, t, tbs, phi, C, DHW, sums); \
-    else hipLaunchKernelGGL((crit_sums_kernel<D_, X_, false>), dim3((unsigned)gx, B * C), dim3(256), 0, ST(stream), o, obs, t, tbs, phi, C, DHW, sums);   \
+    if (vec) hipLaunchKernelGGL((crit_sums_kernel<D_, X_, true, F_>), dim3((unsigned)gx, B * C), dim3(256), 0, ST(stream), o, obs, t, tbs, phi, C, DHW, sums, fg, fa); \
+    else hipLaunchKernelGGL((crit_sums_kernel<D_, X_, false, F_>), dim3((unsigned)gx, B * C), dim3(256), 0, ST(stream), o, obs, t, tbs, phi, C, DHW, sums, fg, fa);   \
   } while (0)
-  if (x4 == X4_PHI) { if (dice) SP_CRIT_SUMS(true, X4_PHI); else SP_CRIT_SUMS(false, X4_PHI); }
-  else if (x4 == X4_BCE) { if (dice) SP_CRIT_SUMS(true, X4_BCE); else SP_CRIT_SUMS(false, X4_BCE); }
-  else SP_CRIT_SUMS(true, X4_NONE);
+  if (first) {
+    if (x4 == X4_FOCAL2) { if (dice) SP_CRIT_SUMS(true, X4_FOCAL2, true); else SP_CRIT_SUMS(false, X4_FOCAL2, true); }
+    else if (x4 == X4_FOCAL) { if (dice) SP_CRIT_SUMS(true, X4_FOCAL, true); else SP_CRIT_SUMS(false, X4_FOCAL, true); }
+    else SP_CRIT_SUMS(true, X4_NONE, true);
+  }
+  else if (x4 == X4_PHI) { if (dice) SP_CRIT_SUMS(true, X4_PHI, false); else SP_CRIT_SUMS(false, X4_PHI, false); }
+  else if (x4 == X4_BCE) { if (dice) SP_CRIT_SUMS(true, X4_BCE, false); else SP_CRIT_SUMS(false, X4_BCE, false); }
+  else SP_CRIT_SUMS(true, X4_NONE, false);
 #undef SP_CRIT_SUMS
 }
 extern "C" int sp_vloss_sums(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, int32_t B, int32_t C, int64_t DHW,
@@ -210,16 +254,31 @@ extern "C" int sp_bloss_sums(const float* o, int64_t o_bstride, const float* t, 
 // one thread: the loss and the backward's coefficients (ca, cb, c3) per channel; then all threads zero the replica rows again.
 // wd / w4: the weights of the Dice term / of the fourth moment, NULL = the term is absent; scale: one float on the device that
 // multiplies w4 (the boundary weight: a captured step follows its schedule), NULL = 1
+// FIRST (sp_tloss_*): the region term is the (focal) Tversky loss on first moments, wd its weights: with TP = sum o*t, N = TP + eps,
+// D = TP + fpw (sum o - TP) + fnw (sum t - TP) + eps and base = 1 - N / D it is wd max(base, 1e-12)^(1 / tg), and (ca, cb) are the
+// coefficients of d / d o = ca*t + cb.  Below the clamp the gradient is zero, as torch's clamp_min has it: a perfectly predicted or an
+// empty channel has base = 0, where base^(1/tg - 1) is 0^(negative).
+template <bool FIRST>
 __global__ void crit_finalize_kernel(double* __restrict__ sums, const float* __restrict__ wd, const float* __restrict__ w4,
                                      const float* __restrict__ scale, double eps, double count, int C, float* __restrict__ loss,
-                                     float* __restrict__ coef) {
+                                     float* __restrict__ coef, double fpw, double fnw, double tg) {
   const int pitch = SP_VLOSS_PITCH(C);
   if (threadIdx.x == 0) {
     const double sc = scale ? (double)scale[0] : 1.0;
     double dice = 0.0, x = 0.0;
     for (int c = 0; c < C; ++c) {
       float ca = 0.f, cb = 0.f, c3 = 0.f;
-      if (wd) {
+      if (FIRST && wd) {
+        const double tp = sp_rows_sum(sums, c * 4, pitch);
+        const double N = tp + eps;
+        const double D = tp + fpw * (sp_rows_sum(sums, c * 4 + 1, pitch) - tp) + fnw * (sp_rows_sum(sums, c * 4 + 2, pitch) - tp) + eps;
+        const double base = 1.0 - N / D;
+        dice += (double)wd[c] * pow(fmax(base, 1e-12), 1.0 / tg);
+        const double k = base >= 1e-12 ? -((double)wd[c] / tg) * pow(base, 1.0 / tg - 1.0) : 0.0;
+        ca = (float)(k * (1.0 / D - N * (1.0 - fpw - fnw) / (D * D)));
+        cb = (float)(-k * N * fpw / (D * D));
+      }
+      if (!FIRST && wd) {
         const double num = 2.0 * sp_rows_sum(sums, c * 4, pitch) + eps;
         const double den = sp_rows_sum(sums, c * 4 + 1, pitch) + sp_rows_sum(sums, c * 4 + 2, pitch) + eps;
         dice += (double)wd[c] * num / den;
@@ -233,7 +292,7 @@ __global__ void crit_finalize_kernel(double* __restrict__ sums, const float* __r
       }
       coef[3 * c] = ca; coef[3 * c + 1] = cb; coef[3 * c + 2] = c3;
     }
-    *loss = (float)((wd ? 1.0 - dice : 0.0) + x);
+    *loss = (float)((wd ? (FIRST ? dice : 1.0 - dice) : 0.0) + x);
   }
   __syncthreads();
   for (int k = threadIdx.x; k < SP_REDUCE_ROWS * pitch; k += blockDim.x) sums[k] = 0.0;
@@ -241,24 +300,30 @@ __global__ void crit_finalize_kernel(double* __restrict__ sums, const float* __r
 extern "C" int sp_vloss_finalize_clear(double* sums, const float* w_dice, const float* w_bce, double eps, double count, int32_t C,
                                        float* loss, float* coef, sp_stream_t stream) {
   SP_CHECK_ARG(sums && (w_dice || w_bce) && loss && coef && C >= 1 && count > 0.0, "sp_vloss_finalize_clear: bad arguments");
-  hipLaunchKernelGGL(crit_finalize_kernel, dim3(1), dim3(64), 0, ST(stream), sums, w_dice, w_bce, (const float*)nullptr, eps, count, C, loss, coef);
+  hipLaunchKernelGGL(crit_finalize_kernel<false>, dim3(1), dim3(64), 0, ST(stream), sums, w_dice, w_bce, (const float*)nullptr, eps, count, C, loss, coef,
+                     0.0, 0.0, 1.0);
   SP_CHECK_LAUNCH("sp_vloss_finalize_clear");
   return SP_OK;
 }
 extern "C" int sp_bloss_finalize_clear(double* sums, const float* w_dice, const float* w_boundary, const float* scale, double eps, double count,
                                        int32_t C, float* loss, float* coef, sp_stream_t stream) {
   SP_CHECK_ARG(sums && w_boundary && scale && loss && coef && C >= 1 && count > 0.0, "sp_bloss_finalize_clear: bad arguments");
-  hipLaunchKernelGGL(crit_finalize_kernel, dim3(1), dim3(64), 0, ST(stream), sums, w_dice, w_boundary, scale, eps, count, C, loss, coef);
+  hipLaunchKernelGGL(crit_finalize_kernel<false>, dim3(1), dim3(64), 0, ST(stream), sums, w_dice, w_boundary, scale, eps, count, C, loss, coef,
+                     0.0, 0.0, 1.0);
   SP_CHECK_LAUNCH("sp_bloss_finalize_clear");
   return SP_OK;
 }
 // do[b,c,v] = up * (ca[c]*t + cb[c]*o + c3[c]*X'), X' = phi (PHI) or (o - t)/max(o(1 - o), 1e-12); grid as crit_sums_kernel: the
 // coefficients are uniform over a workgroup.  Without phi a channel that has no BCE term (c3 == 0) takes the loop without the division.
-template <bool PHI, bool VEC>
+// X: X4_BCE (sp_vloss_*), X4_PHI (sp_bloss_*) or, with first moments -- up * (ca*t + cb + c3*fl') --, X4_FOCAL2 / X4_FOCAL (sp_tloss_*:
+// a channel without a focal term takes the loop without the logarithms).
+template <int X, bool VEC>
 __global__ __launch_bounds__(256) void crit_bwd_kernel(const float* __restrict__ o, int64_t obs, const float* __restrict__ t, int64_t tbs,
                                                        const float* __restrict__ phi, const float* __restrict__ coef,
-                                                       const float* __restrict__ upstream, int C, int64_t DHW, float* __restrict__ d) {
-  constexpr int XA = PHI ? X4_PHI : X4_BCE, XB = PHI ? X4_PHI : X4_NONE;      // the loop with c3 != 0 / with c3 == 0
+                                                       const float* __restrict__ upstream, int C, int64_t DHW, float* __restrict__ d,
+                                                       float fg, float fa) {
+  constexpr bool PHI = X == X4_PHI, FIRST = X == X4_FOCAL2 || X == X4_FOCAL;
+  constexpr int XA = X, XB = PHI ? X4_PHI : X4_NONE;      // the loop with c3 != 0 / with c3 == 0
   const int bc = blockIdx.y, c = bc % C, b = bc / C;
   const float up = upstream ? *upstream : 1.f;
   const float ca = up * coef[3 * c], cb = up * coef[3 * c + 1], c3 = up * coef[3 * c + 2];
@@ -277,29 +342,32 @@ __global__ __launch_bounds__(256) void crit_bwd_kernel(const float* __restrict__
       const float4 a = o4[i], bb = t4[i];
       float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
       if (PHI) p = p4[i];
-      d4[i] = xa ? make_float4(crit_grad<XA>(a.x, bb.x, p.x, ca, cb, c3), crit_grad<XA>(a.y, bb.y, p.y, ca, cb, c3),
-                               crit_grad<XA>(a.z, bb.z, p.z, ca, cb, c3), crit_grad<XA>(a.w, bb.w, p.w, ca, cb, c3))
-                 : make_float4(crit_grad<XB>(a.x, bb.x, p.x, ca, cb, c3), crit_grad<XB>(a.y, bb.y, p.y, ca, cb, c3),
-                               crit_grad<XB>(a.z, bb.z, p.z, ca, cb, c3), crit_grad<XB>(a.w, bb.w, p.w, ca, cb, c3));
+      d4[i] = xa ? make_float4(crit_grad<XA, FIRST>(a.x, bb.x, p.x, ca, cb, c3, fg, fa), crit_grad<XA, FIRST>(a.y, bb.y, p.y, ca, cb, c3, fg, fa),
+                               crit_grad<XA, FIRST>(a.z, bb.z, p.z, ca, cb, c3, fg, fa), crit_grad<XA, FIRST>(a.w, bb.w, p.w, ca, cb, c3, fg, fa))
+                 : make_float4(crit_grad<XB, FIRST>(a.x, bb.x, p.x, ca, cb, c3), crit_grad<XB, FIRST>(a.y, bb.y, p.y, ca, cb, c3),
+                               crit_grad<XB, FIRST>(a.z, bb.z, p.z, ca, cb, c3), crit_grad<XB, FIRST>(a.w, bb.w, p.w, ca, cb, c3));
     }
   } else if (PHI) {      // written out, t loaded first: the order of the loads decides which of the products the compiler fuses
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < DHW; i += (int64_t)gridDim.x * 256) dp[i] = ca * tp[i] + cb * op[i] + c3 * pp[i];
   } else if (xa) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < DHW; i += (int64_t)gridDim.x * 256) dp[i] = crit_grad<XA>(op[i], tp[i], 0.f, ca, cb, c3);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < DHW; i += (int64_t)gridDim.x * 256) dp[i] = crit_grad<XA, FIRST>(op[i], tp[i], 0.f, ca, cb, c3, fg, fa);
   } else {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < DHW; i += (int64_t)gridDim.x * 256) dp[i] = crit_grad<XB>(op[i], tp[i], 0.f, ca, cb, c3);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < DHW; i += (int64_t)gridDim.x * 256) dp[i] = crit_grad<XB, FIRST>(op[i], tp[i], 0.f, ca, cb, c3);
   }
 }
+// x: X4_BCE, X4_FOCAL2 or X4_FOCAL without phi
 static void crit_bwd_launch(const float* o, int64_t obs, const float* t, int64_t tbs, const float* phi, const float* coef, const float* upstream,
-                            int32_t B, int32_t C, int64_t DHW, float* dout, sp_stream_t stream) {
+                            int32_t B, int32_t C, int64_t DHW, float* dout, sp_stream_t stream, int x = X4_BCE, float fg = 0.f, float fa = 0.f) {
   const bool vec = crit_vec_ok(o, obs, B, DHW) && crit_vec_ok(t, tbs, B, DHW) && (!phi || crit_vec_ok(phi, 0, 1, DHW)) && crit_vec_ok(dout, 0, 1, DHW);
   const int64_t per = vec ? 256 * 4 : 256;                                  // elements per workgroup and trip
   int64_t gx = (DHW + per - 1) / per, cap = LOSS_MAX_BLOCKS / ((int64_t)B * C);
   if (cap < 1) cap = 1;
   if (gx > cap) gx = cap;
-#define SP_CRIT_BWD(P_, V_) hipLaunchKernelGGL((crit_bwd_kernel<P_, V_>), dim3((unsigned)gx, B * C), dim3(256), 0, ST(stream), o, obs, t, tbs, phi, coef, upstream, C, DHW, dout)
-  if (phi) { if (vec) SP_CRIT_BWD(true, true); else SP_CRIT_BWD(true, false); }
-  else { if (vec) SP_CRIT_BWD(false, true); else SP_CRIT_BWD(false, false); }
+#define SP_CRIT_BWD(X_, V_) hipLaunchKernelGGL((crit_bwd_kernel<X_, V_>), dim3((unsigned)gx, B * C), dim3(256), 0, ST(stream), o, obs, t, tbs, phi, coef, upstream, C, DHW, dout, fg, fa)
+  if (phi) { if (vec) SP_CRIT_BWD(X4_PHI, true); else SP_CRIT_BWD(X4_PHI, false); }
+  else if (x == X4_FOCAL2) { if (vec) SP_CRIT_BWD(X4_FOCAL2, true); else SP_CRIT_BWD(X4_FOCAL2, false); }
+  else if (x == X4_FOCAL) { if (vec) SP_CRIT_BWD(X4_FOCAL, true); else SP_CRIT_BWD(X4_FOCAL, false); }
+  else { if (vec) SP_CRIT_BWD(X4_BCE, true); else SP_CRIT_BWD(X4_BCE, false); }
 #undef SP_CRIT_BWD
 }
 extern "C" int sp_vloss_bwd(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* coef, const float* upstream,
@@ -314,6 +382,34 @@ extern "C" int sp_bloss_bwd(const float* o, int64_t o_bstride, const float* t, i
   SP_CHECK_ARG(crit_args_ok(o, o_bstride, t, t_bstride, B, C, DHW) && phi && coef && dout, "sp_bloss_bwd: bad arguments");
   crit_bwd_launch(o, o_bstride, t, t_bstride, phi, coef, upstream, B, C, DHW, dout, stream);
   SP_CHECK_LAUNCH("sp_bloss_bwd");
+  return SP_OK;
+}
+// the Tversky / focal entry points: first moments in the region columns, the focal cross entropy in the fourth
+static inline bool focal_args_ok(float g, float al) { return (g == 0.f || g >= 1.f) && al >= 0.f && al <= 1.f; }
+extern "C" int sp_tloss_sums(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, int32_t B, int32_t C, int64_t DHW,
+                             int32_t terms, float focal_gamma, float focal_alpha, double* sums, sp_stream_t stream) {
+  SP_CHECK_ARG(crit_args_ok(o, o_bstride, t, t_bstride, B, C, DHW) && sums && terms >= 1 && terms <= (SP_TLOSS_TVERSKY | SP_TLOSS_FOCAL) &&
+               (!(terms & SP_TLOSS_FOCAL) || focal_args_ok(focal_gamma, focal_alpha)), "sp_tloss_sums: bad arguments");
+  crit_sums_launch(o, o_bstride, t, t_bstride, nullptr, B, C, DHW, terms & SP_TLOSS_TVERSKY,
+                   terms & SP_TLOSS_FOCAL ? (focal_gamma == 2.f ? X4_FOCAL2 : X4_FOCAL) : X4_NONE, sums, stream, true, focal_gamma, focal_alpha);
+  SP_CHECK_LAUNCH("sp_tloss_sums");
+  return SP_OK;
+}
+extern "C" int sp_tloss_finalize_clear(double* sums, const float* w_tversky, const float* w_focal, double fp_weight, double fn_weight,
+                                       double tversky_gamma, double eps, double count, int32_t C, float* loss, float* coef, sp_stream_t stream) {
+  SP_CHECK_ARG(sums && (w_tversky || w_focal) && loss && coef && C >= 1 && count > 0.0 && fp_weight >= 0.0 && fn_weight >= 0.0 && tversky_gamma >= 1.0,
+               "sp_tloss_finalize_clear: bad arguments");
+  hipLaunchKernelGGL(crit_finalize_kernel<true>, dim3(1), dim3(64), 0, ST(stream), sums, w_tversky, w_focal, (const float*)nullptr, eps, count, C, loss,
+                     coef, fp_weight, fn_weight, tversky_gamma);
+  SP_CHECK_LAUNCH("sp_tloss_finalize_clear");
+  return SP_OK;
+}
+extern "C" int sp_tloss_bwd(const float* o, int64_t o_bstride, const float* t, int64_t t_bstride, const float* coef, const float* upstream,
+                            float focal_gamma, float focal_alpha, int32_t B, int32_t C, int64_t DHW, float* dout, sp_stream_t stream) {
+  SP_CHECK_ARG(crit_args_ok(o, o_bstride, t, t_bstride, B, C, DHW) && coef && dout && focal_args_ok(focal_gamma, focal_alpha), "sp_tloss_bwd: bad arguments");
+  crit_bwd_launch(o, o_bstride, t, t_bstride, nullptr, coef, upstream, B, C, DHW, dout, stream, focal_gamma == 2.f ? X4_FOCAL2 : X4_FOCAL, focal_gamma,
+                  focal_alpha);
+  SP_CHECK_LAUNCH("sp_tloss_bwd");
   return SP_OK;
 }
 

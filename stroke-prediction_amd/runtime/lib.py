@@ -95,6 +95,7 @@ BnFinArgs, BnBwdArgs, ConvArgs, WgradArgs, WgradF8Args, ConvFcArgs, Conv3dDesc, 
 SP_BF16, SP_F32, SP_HL, SP_REDUCE_ROWS = (CONSTS[n] for n in ("SP_BF16", "SP_F32", "SP_HL", "SP_REDUCE_ROWS"))
 ACT_NONE, ACT_LEAKY, ACT_ELU, ACT_SIGMOID = (CONSTS["SP_ACT_" + n] for n in ("NONE", "LEAKY", "ELU", "SIGMOID"))
 SP_VLOSS_DICE, SP_VLOSS_BCE = CONSTS["SP_VLOSS_DICE"], CONSTS["SP_VLOSS_BCE"]      # the terms of the sp_vloss_* / sp_cae_loss_crit_* calls
+SP_TLOSS_TVERSKY, SP_TLOSS_FOCAL = CONSTS["SP_TLOSS_TVERSKY"], CONSTS["SP_TLOSS_FOCAL"]      # the terms of the sp_tloss_* calls
 
 
 def SP_VLOSS_PITCH(C):
@@ -104,6 +105,11 @@ def SP_VLOSS_PITCH(C):
 
 def SP_BLOSS_PITCH(C):
     """row pitch (doubles) of the sp_bloss_* accumulator: the header's SP_BLOSS_PITCH = SP_VLOSS_PITCH"""
+    return SP_VLOSS_PITCH(C)
+
+
+def SP_TLOSS_PITCH(C):
+    """row pitch (doubles) of the sp_tloss_* accumulator: the header's SP_TLOSS_PITCH = SP_VLOSS_PITCH"""
     return SP_VLOSS_PITCH(C)
 
 
