@@ -942,6 +942,28 @@ int sp_adam_step_flat_dev(float* p, const float* g, float* m, float* v, int64_t 
 int sp_adam_step_flat_hyp(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper_dev,
                           const int32_t* step_dev, float grad_scale, sp_stream_t stream);
 
+/* ------------------------------------------------------------------ the fused optimiser family (csrc/sp_optim.hip): Adam, AdamW
+ * (decoupled weight decay), SGD with momentum and SGD-Nesterov on flat fp32 buffers, with torch's global-norm gradient clipping
+ * (clip_grad_norm_) folded into the update.  sp_adam_step_flat* above are untouched. */
+enum { SP_OPT_ADAM = 0, SP_OPT_ADAMW = 1, SP_OPT_SGD = 2, SP_OPT_SGD_NESTEROV = 3 };
+
+/* stage 1 of the squared gradient norm: a launch of npartials (1..256) workgroups; workgroup b writes the sum of g[i]^2 over its
+ * grid-stride slice to partials[b] as a double (accumulate != 0: adds it to what partials[b] holds, for a norm over several
+ * tensors).  No atomics, one fixed order: the same bits on every run. */
+int sp_grad_sqnorm_partials(const float* g, int64_t n, double* partials, int32_t npartials, int32_t accumulate,
+                            sp_stream_t stream);
+
+/* one update of kind SP_OPT_*.  hyper_dev holds {lr, beta1, beta2, eps, weight_decay, max_norm, momentum, -} and step_dev the
+ * 1-based step count, both in device memory as for sp_adam_step_flat_hyp (step_dev may be NULL for the SGD kinds, which do not
+ * read it, as may v; m is their momentum buffer).  gi = g[i] * grad_scale * coef, where coef = 1 unless partials != NULL and
+ * max_norm > 0: then norm = grad_scale * sqrt(sum of the npartials doubles), coef = min(1, max_norm / (norm + 1e-6)), and norm is
+ * written to norm_dev.  ADAM: gi += wd * p, then Adam (with clipping off: the bits of sp_adam_step_flat_hyp).  ADAMW:
+ * p *= 1 - lr * wd, then Adam.  SGD: gi += wd * p; m = momentum * m + gi; p -= lr * m.  SGD_NESTEROV: p -= lr * (gi + momentum * m).
+ * 16-byte accesses where p, g, m (and v) are 16-byte aligned, element accesses otherwise. */
+int sp_optim_step_flat(int32_t kind, float* p, const float* g, float* m, float* v, int64_t n, const float* hyper_dev,
+                       const int32_t* step_dev, float grad_scale, const double* partials, int32_t npartials,
+                       float* norm_dev, sp_stream_t stream);
+
 /* ------------------------------------------------------------------ data-parallel gradient exchange (RCCL over xGMI)
  * The reference has no distributed code; the path shards by batch and needs ONE collective per step, the sum of the flat
  * fp32 gradient buffer over the replicas (learner/Learner.py:120-122 per replica).  comm is an ncclComm_t of

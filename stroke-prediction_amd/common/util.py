@@ -56,6 +56,20 @@ _EXPERIMENT = [
                           help="(MI355X build) --criterion focalbce / tverskyfocalbce: weight of the foreground voxels in [0, 1] (default 0.25)")),
     ("--focalweight", dict(type=float, default=None,
                            help="(MI355X build) --criterion tverskyfocalbce: weight of the focal cross entropy beside the Tversky term (default 1)")),
+    ("--optimizer", dict(type=str, default="adam", choices=["adam", "adamw", "sgd"],
+                         help="(MI355X build) optim.make_optimizer: Adam as the reference (torch.optim.Adam, or FusedAdam under --fusedadam / "
+                              "--graph / --clipnorm), AdamW (decoupled weight decay) or SGD with momentum (nnU-Net: momentum 0.99, "
+                              "Nesterov, poly learning rate, gradients clipped at norm 12); adamw and sgd are always the fused classes")),
+    ("--lr", dict(type=float, default=None, help="(MI355X build) learning rate (default 1e-3, --optimizer sgd 1e-2)")),
+    ("--momentum", dict(type=float, default=0.99, help="(MI355X build) --optimizer sgd: momentum")),
+    ("--nesterov", dict(action=argparse.BooleanOptionalAction, default=True, help="(MI355X build) --optimizer sgd: Nesterov momentum")),
+    ("--weightdecay", dict(type=float, default=None, help="(MI355X build) weight decay (default: the script's own 1e-5)")),
+    ("--clipnorm", dict(type=float, default=0.0,
+                        help="(MI355X build) clip the global gradient norm at this value inside the fused step (clip_grad_norm_ "
+                             "semantics, no host read: works under --graph); 0 = off.  With --optimizer adam it selects FusedAdam")),
+    ("--lrschedule", dict(type=str, default="multistep", choices=["multistep", "poly"],
+                          help="(MI355X build) MultiStepLR at --lrsteps (none without them), or PolynomialLR over --epochs with --lrpower")),
+    ("--lrpower", dict(type=float, default=0.9, help="(MI355X build) --lrschedule poly: the exponent")),
 ]
 _CAE = [
     ("--epochs", dict(type=int, default=300, help="Number of epochs")),

@@ -26,7 +26,9 @@ class CaeReconstructionLearner(Learner, CaeInference):
         self._verbose = verbose
 
     def adapt_betas(self, epoch):
-        betas = self._optimizer.defaults['betas']
+        betas = self._optimizer.defaults.get('betas')
+        if betas is None:                     # (--optimizer sgd: no betas to warm up)
+            return
         if epoch > self.N_EPOCHS_ADAPT_BETA1:
             return
         if epoch < self.N_EPOCHS_ADAPT_BETA1:

@@ -257,7 +257,7 @@ class Learner(Inference):
     def _optimise_graph(self, batch: dict, epoch):
         if not getattr(self._optimizer, "capturable", False):
             raise RuntimeError("Learner(graph=True) needs an optimiser whose step can be captured and whose hyper-parameters "
-                               "live on the device: stroke_prediction_amd.optim.FusedAdam(..., capturable=True)")
+                               "live on the device: stroke_prediction_amd.optim.FusedAdam / FusedAdamW / FusedSGD(..., capturable=True)")
         dev = next(self._model.parameters()).device
         tensors = {k: v for k, v in batch.items() if torch.is_tensor(v)}
         key = (tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(tensors.items())), self.graph_key(epoch))

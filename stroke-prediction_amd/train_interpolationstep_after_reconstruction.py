@@ -14,6 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import stroke_prediction_amd  # noqa: E402,F401
+from stroke_prediction_amd import optim  # noqa: E402
 from common import data, metrics, util  # noqa: E402
 from common.model.Cae3D import Cae3D, Enc3DStep  # noqa: E402
 from learner.CaeStepLearner import CaeStepLearner  # noqa: E402
@@ -37,8 +38,9 @@ def train(args):
     cae = build_model(args)
     params = [p for p in cae.parameters() if p.requires_grad]
     print('# optimizing params', sum(p.nelement() for p in params), '/ total: cae', sum(p.nelement() for p in cae.parameters()))
-    optimizer = torch.optim.Adam(params, lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999))
-    scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, args.lrsteps) if args.lrsteps else None
+    # torch.optim.Adam unless --optimizer / --clipnorm ask for a fused class (CaeStepLearner replays no captured step)
+    optimizer = optim.make_optimizer(args, params, dict(lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999)), graph=False, fusedadam=False)
+    scheduler = optim.make_scheduler(args, optimizer)
     common = [data.ResamplePlaneXY(args.xyresample)]
     # --batchaugment: flip + elastic deformation once per collated batch instead of once per sample and channel
     augment = [] if args.batchaugment else [data.HemisphericFlip(), data.ElasticDeform()]

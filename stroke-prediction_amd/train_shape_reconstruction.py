@@ -17,6 +17,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import stroke_prediction_amd  # noqa: E402,F401
+from stroke_prediction_amd import optim  # noqa: E402
 from common import data, metrics, util  # noqa: E402
 from common.model.Cae3D import Cae3D, Dec3D, Enc3D, Enc3DStep  # noqa: E402
 from learner.CaeReconstructionLearner import CaeReconstructionLearner  # noqa: E402
@@ -38,13 +39,8 @@ def build_optimizer(args, cae):
     params = [p for p in cae.parameters() if p.requires_grad]
     print('# optimizing params', sum(p.nelement() for p in params), '/ total: cae', sum(p.nelement() for p in cae.parameters()))
     hyper = dict(lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999))
-    if args.fusedadam or args.graph:
-        from stroke_prediction_amd.optim import FusedAdam
-        optimizer = FusedAdam(params, capturable=args.graph, **hyper)
-    else:
-        optimizer = torch.optim.Adam(params, **hyper)
-    scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, args.lrsteps) if args.lrsteps else None
-    return optimizer, scheduler
+    optimizer = optim.make_optimizer(args, params, hyper)      # --optimizer / --clipnorm / --fusedadam / --graph
+    return optimizer, optim.make_scheduler(args, optimizer)
 
 
 def build_loaders(args):

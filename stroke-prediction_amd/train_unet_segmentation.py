@@ -18,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import stroke_prediction_amd  # noqa: E402,F401
+from stroke_prediction_amd import optim  # noqa: E402
 from common import data, metrics, util  # noqa: E402
 from common.model.Unet3D import Unet3D  # noqa: E402
 from learner.UnetSegmentationLearner import UnetSegmentationLearner  # noqa: E402
@@ -47,12 +48,8 @@ def train(args):
     params = [p for p in unet.parameters() if p.requires_grad]
     print('# optimizing params', sum(p.nelement() for p in params), '/ total: unet', sum(p.nelement() for p in unet.parameters()))
     hyper = dict(lr=1e-3, weight_decay=1e-5, betas=(0.99, 0.999))
-    if args.fusedadam or args.graph:
-        from stroke_prediction_amd.optim import FusedAdam
-        optimizer = FusedAdam(params, capturable=args.graph, **hyper)
-    else:
-        optimizer = torch.optim.Adam(params, **hyper)
-    scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, args.lrsteps) if args.lrsteps else None
+    optimizer = optim.make_optimizer(args, params, hyper)      # --optimizer / --clipnorm / --fusedadam / --graph
+    scheduler = optim.make_scheduler(args, optimizer)
     ds_train, ds_valid = build_loaders(args)
     criterion = metrics.make_criterion(args.criterion)
     metrics.configure_criterion(criterion, args)      # --boundaryweight / --boundaryramp; nothing for the other criteria
