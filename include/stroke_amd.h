@@ -1018,6 +1018,43 @@ int sp_elastic_warp_batch(const float* src0, float* dst0, int32_t C0, const floa
                           const int32_t* flip, int32_t B, int32_t Z, int32_t Y, int32_t X, float alpha, float alpha_z,
                           sp_stream_t stream);
 
+/* ------------------------------------------------------------------ batch-level intensity augmentation (csrc/sp_intensity.hip)
+ * data.py:IntensityAugment.  A field is one (sample, image channel) volume of per_field = Z * Y * X fp32 voxels, X contiguous;
+ * nfields (<= 65535) fields lie adjacent in memory, per_field < 2^31.  Stages, in this order: blur, noise, brightness, contrast,
+ * gamma.
+ * sp_blur3d_reflect_batch = scipy.ndimage.gaussian_filter(field, sigma) with mode="reflect" (d c b a | a b c d | d c b a), one
+ * sigma per field, three launches in all: passes along x, then y, then z.  weights (device, float[nfields][2 radius + 1]): row f
+ * holds the taps of field f, lowest offset first, zero-padded to the common radius (<= 64); tap sums run lowest to highest with
+ * fmaf.  A row whose centre tap is 1.0 (the delta kernel) copies its field bit for bit.  Index i outside a line of n elements
+ * reads -i - 1 (i < 0) or 2n - 1 - i (i >= n): one reflection, so every extent must be >= radius (SP_EINVAL otherwise).  tmp =
+ * scratch of the size of src; src, dst, tmp: three different buffers.  Nothing crosses from one field into the next. */
+int sp_blur3d_reflect_batch(const float* src, float* dst, float* tmp, const float* weights, int32_t nfields, int32_t Z, int32_t Y,
+                            int32_t X, int32_t radius, sp_stream_t stream);
+/* params (device, float[nfields][8]): row f = [sigma_n, gain, contrast, gamma, invert, 0, 0, 0] of field f, gain, contrast,
+ * gamma > 0.  y1[e] = src[e] + sigma_n * n(e) with n(e) a standard normal: Philox4x32-10, key (seed & 0xffffffff, seed >> 32),
+ * counter (e >> 2, 0x80000000 | f, call & 0xffffffff, call >> 32); words (w0, w1) give elements 4q and 4q + 1, (w2, w3) give
+ * 4q + 2 and 4q + 3 by Box-Muller: u1 = ((w >> 8) + 1) 2^-24, u2 = (w' >> 8) 2^-24, r = sqrt(-2 ln u1), the even element
+ * r cos(2 pi u2), the odd one r sin(2 pi u2).  The value depends on (seed, call, f, e) alone; sigma_n = 0 skips the stage.  seed
+ * and call are the 64 bits of an unsigned value.
+ * sp_intensity_stats_partials writes partials (device, 16-byte aligned, float[nfields][64][4]) = (min, max, sum, 0) of y1 over
+ * 64 contiguous chunks of ceil(per_field / 64) elements rounded up to a multiple of 4 (chunks behind the field's end hold
+ * (+inf, -inf, 0, 0)).  Fixed-order reduction, no atomics: equal inputs give equal bits, and a field's partials do not depend on
+ * nfields.  src is read with 16-byte loads when per_field is a multiple of 4 and src is 16-byte aligned. */
+int sp_intensity_stats_partials(const float* src, const float* params, float* partials, int32_t nfields, int64_t per_field,
+                                int64_t seed, int64_t call, sp_stream_t stream);
+/* One launch over all fields; src == dst is allowed (each work item reads and writes the same four voxels).  Per field, from its
+ * partials in index order (sum in double): min1, max1, mean1 = sum / per_field of y1; then with g = gain, k = contrast:
+ *   y2 = g y1;  min2 = g min1, max2 = g max1, m2 = g mean1
+ *   y3 = f(y2) = min(max(fmaf(y2 - m2, k, m2), min2), max2);  min3 = f(min2), max3 = f(max2)
+ *   R = max3 - min3;  y4 = ((y3 - min3) / (R + 1e-7))^gamma R + min3, or, invert != 0 (gamma of the negated image):
+ *   y4 = max3 - ((max3 - y3) / (R + 1e-7))^gamma R
+ * all in fp32, no contraction.  A stage with a neutral parameter (sigma_n = 0, g = 1, k = 1, gamma = 1 and invert = 0) is
+ * skipped, not computed: a field with an all-neutral row is copied bit for bit, and partials are read only for contrast or gamma.
+ * The same seed and call as in sp_intensity_stats_partials regenerate the same noise.  16-byte loads and stores when per_field is a
+ * multiple of 4 and src and dst are 16-byte aligned, element-wise otherwise. */
+int sp_intensity_apply_batch(const float* src, float* dst, const float* params, const float* partials, int32_t nfields, int64_t per_field,
+                             int64_t seed, int64_t call, sp_stream_t stream);
+
 /* ------------------------------------------------------------------ batched patch gather from the device-resident case cache
  * (common/data.py: DeviceCaseCache / CachedBatchLoader; csrc/sp_gather.hip).  One launch.  src0 (N, C0, Z, Y, X) /
  * src1 (N, C1, Z, Y, X): the cached cases, fp32, X contiguous (the ToTensor layout); either group may be empty (C = 0, its

@@ -17,6 +17,8 @@ every case on the device (``DeviceCaseCache``) and builds each batch -- flip, pa
 that launch ``sp_patch_sample_batch`` (csrc/sp_sample.hip): rotation, scaling, elastic deformation and an intensity change per
 sample, images and labels through one field, in the kernel that builds the batch.  ``ForegroundOversample`` (``foreground=``) forces
 a share of each cached batch onto lesion: ``sp_patch_origins_fg`` (csrc/sp_fgpatch.hip) rewrites those samples' origins on the device.
+``IntensityAugment`` is a second ``batch_transform``: blur, noise, brightness, contrast and gamma of the images of a batch that already
+sits on the device, in two launches (five with blur; csrc/sp_intensity.hip).
 """
 import datetime
 import random
@@ -844,6 +846,177 @@ def _sample_launch(cache, table, ext0, pad0, padval0, ext1, pad1, augment, foreg
            O.ptr(xform_dev), O.ptr(fields) if fields is not None else None, O.ptr(inten_dev) if inten_dev is not None else None,
            len(cache), B, Z, Y, X, O.stream())
     return (dst0 if dst0 is not None else []), (dst1 if dst1 is not None else []), table_dev
+
+
+def _pair(name, pair, who="IntensityAugment"):
+    if len(pair) != 2 or not pair[0] <= pair[1]:
+        raise ValueError("%s: %s is a (low, high) pair, got %r" % (who, name, pair))
+    return (float(pair[0]), float(pair[1]))
+
+
+def gaussian_weights(sigma, radius=None, truncate=4.0):
+    """The taps of ``scipy.ndimage.gaussian_filter(sigma, truncate)`` (``_gaussian_kernel1d``): ``exp(-x^2 / (2 sigma^2))`` for
+    ``x = -r .. r``, ``r = int(truncate sigma + 0.5)``, normalised in float64; centred in a row of ``2 radius + 1`` zeros when a
+    larger ``radius`` is given."""
+    r = int(truncate * float(sigma) + 0.5)
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (float(sigma) * float(sigma)) * x ** 2)
+    phi = phi / phi.sum()
+    if radius is None or radius == r:
+        return phi
+    if radius < r:
+        raise ValueError("gaussian_weights: sigma %r needs radius %d, got %d" % (sigma, r, radius))
+    out = np.zeros(2 * radius + 1)
+    out[radius - r:radius + r + 1] = phi
+    return out
+
+
+class IntensityAugment(object):
+    """Intensity augmentation of a collated batch on the device, a callable ``batch -> batch`` for ``batch_transform=`` on the loader
+    factories: Gaussian blur, Gaussian noise, brightness, contrast and gamma of ``batch['images']`` ((B, C0, Z, Y, X) CUDA fp32), with
+    batchgenerators' / nnU-Net's ranges and probabilities as defaults.  Labels and every other key pass through untouched; the
+    images come back as a new tensor.  There is no CPU path.  Two launches per batch (``sp_intensity_stats_partials``,
+    ``sp_intensity_apply_batch``), five when a field blurs (three passes of ``sp_blur3d_reflect_batch`` first), one pinned upload
+    of the parameter table and the blur weights, no host read, no synchronisation (csrc/sp_intensity.hip).
+
+    A field is one (sample, channel) volume.  Tosses are per sample, parameters per field.  The stages, in this fixed order:
+
+    1. blur, ``p_blur`` per sample and then ``p_blur_channel`` per channel: ``scipy.ndimage.gaussian_filter(x, sigma)``
+       (``mode="reflect"``, ``truncate=4``), ``sigma`` uniform in ``blur_sigma``.  Every extent must reach the radius ``int(4 sigma + .5)``.
+    2. noise, ``p_noise``: ``y + sqrt(variance) n`` with ``variance`` uniform in ``noise_variance`` and ``n`` standard normal (Philox4x32-10
+       + Box-Muller keyed by (``seed``, call, field, voxel); the call counter advances by one per batch).
+    3. brightness, ``p_gain``: ``g y``, ``g`` uniform in ``gain``.
+    4. contrast, ``p_contrast``: ``clamp((y - mean) k + mean, min, max)`` with the field's own mean and range (batchgenerators'
+       ``preserve_range=True``); ``k`` below 1 or above 1 with equal probability, uniform in that part of ``contrast``.
+    5. gamma: ``((y - min) / (range + 1e-7))^gamma range + min``, ``gamma`` drawn like ``k`` from ``gamma``.  With ``p_gamma_invert``
+       the inverted form (the same transform of ``-y``); otherwise with ``p_gamma`` the plain one.  ``retain_stats`` is not implemented.
+
+    Differences from nnU-Net, on purpose: blur comes BEFORE noise (nnU-Net adds the noise first), so that the noise can be
+    regenerated from its counter in the statistics pass and in the apply pass instead of being stored; each field takes at most
+    one gamma (nnU-Net may apply the inverted and the plain one in a row).  The noise variance is absolute: it assumes inputs
+    of roughly unit scale.  Voxels that ``PadImages`` wrote are treated as image -- a batch-level transform cannot tell them
+    apart, and batchgenerators treats its padding the same way.
+
+    Every host draw comes from this object's own ``numpy.random.RandomState(seed)`` -- the same number of draws per batch whatever
+    the tosses say -- never from Python's ``random``.  A run is reproducible from ``seed`` alone."""
+
+    def __init__(self, noise_variance=(0, 0.1), p_noise=0.1, blur_sigma=(0.5, 1.0), p_blur=0.2, p_blur_channel=0.5,
+                 gain=(0.75, 1.25), p_gain=0.15, contrast=(0.75, 1.25), p_contrast=0.15, gamma=(0.7, 1.5), p_gamma=0.3,
+                 p_gamma_invert=0.1, seed=None):
+        self.noise_variance, self.blur_sigma = _pair("noise_variance", noise_variance), _pair("blur_sigma", blur_sigma)
+        self.gain, self.contrast, self.gamma = _pair("gain", gain), _pair("contrast", contrast), _pair("gamma", gamma)
+        if self.noise_variance[0] < 0:
+            raise ValueError("IntensityAugment: noise_variance must not be negative, got %r" % (noise_variance,))
+        for name, pair in (("blur_sigma", self.blur_sigma), ("gain", self.gain), ("contrast", self.contrast), ("gamma", self.gamma)):
+            if not pair[0] > 0:
+                raise ValueError("IntensityAugment: %s must be positive, got %r" % (name, pair))
+        if int(4.0 * self.blur_sigma[1] + 0.5) > 64:
+            raise ValueError("IntensityAugment: blur_sigma %r needs a radius above 64" % (blur_sigma,))
+        probs = dict(p_noise=p_noise, p_blur=p_blur, p_blur_channel=p_blur_channel, p_gain=p_gain, p_contrast=p_contrast, p_gamma=p_gamma,
+                     p_gamma_invert=p_gamma_invert)
+        for name, p in probs.items():
+            if not 0 <= p <= 1:
+                raise ValueError("IntensityAugment: %s is a probability, got %r" % (name, p))
+            setattr(self, name, float(p))
+        if seed is None:
+            seed = datetime.datetime.now().second + datetime.datetime.now().microsecond
+        self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._rs = np.random.RandomState(self._seed & 0xFFFFFFFF)
+        self._calls = 0
+
+    def _split_uniform(self, pair, shape):
+        """batchgenerators' draw of a contrast factor or a gamma: below 1 or above 1 with equal probability where the range holds
+        both, uniform in that part; always the same three draws"""
+        rs, (lo, hi) = self._rs, pair
+        coin, below, above = rs.rand(*shape), rs.uniform(lo, min(hi, 1.0), shape), rs.uniform(max(lo, 1.0), hi, shape)
+        if hi <= 1:
+            return below
+        if lo >= 1:
+            return above
+        return np.where(coin < 0.5, below, above)
+
+    def draw(self, B, C0):
+        """The host draws of one batch: ``params`` (B * C0, 8) fp32, row ``b * C0 + c`` = [sigma_n, gain, contrast, gamma, invert, 0, 0, 0]
+        with the neutral value where a toss failed; ``weights`` (B * C0, 2 * radius + 1) fp32, the blur taps of every field (the
+        delta kernel for a field that does not blur), or ``None`` when no field blurs; ``radius``: the largest radius of the batch;
+        ``call``: the noise call counter of this batch."""
+        rs, C = self._rs, max(C0, 1)
+        toss = rs.rand(B, 6)                  # noise, blur, gain, contrast, gamma, inverted gamma
+        toss_channel = rs.rand(B, C)          # blur, per channel
+        variance = rs.uniform(self.noise_variance[0], self.noise_variance[1], (B, C))
+        sigma = rs.uniform(self.blur_sigma[0], self.blur_sigma[1], (B, C))
+        gain = rs.uniform(self.gain[0], self.gain[1], (B, C))
+        k = self._split_uniform(self.contrast, (B, C))
+        gamma = self._split_uniform(self.gamma, (B, C))
+        call = self._calls
+        self._calls += 1
+        on = lambda i, p: (toss[:, i] < p)[:, None]
+        invert = on(5, self.p_gamma_invert)
+        params = np.zeros((B, C, 8), dtype=np.float32)
+        params[:, :, 0] = np.where(on(0, self.p_noise), np.sqrt(variance), 0.0)
+        params[:, :, 1] = np.where(on(2, self.p_gain), gain, 1.0)
+        params[:, :, 2] = np.where(on(3, self.p_contrast), k, 1.0)
+        params[:, :, 3] = np.where(invert | on(4, self.p_gamma), gamma, 1.0)
+        params[:, :, 4] = np.where(invert, 1.0, 0.0)
+        params = params[:, :C0].reshape(B * C0, 8)
+        blur = (on(1, self.p_blur) & (toss_channel < self.p_blur_channel))[:, :C0].reshape(-1)
+        weights, radius = None, 0
+        if blur.any():
+            sig = sigma[:, :C0].reshape(-1)
+            radius = max(int(4.0 * s + 0.5) for s in sig[blur])
+            weights = np.zeros((B * C0, 2 * radius + 1), dtype=np.float32)
+            weights[:, radius] = 1.0
+            for f in np.nonzero(blur)[0]:
+                weights[f] = gaussian_weights(sig[f], radius)
+        return {"params": params, "weights": weights, "radius": radius, "call": call}
+
+    def __call__(self, batch):
+        images = batch.get(KEY_IMAGES, [])
+        _require_intensity_input(images)
+        B, C0 = int(images.shape[0]), int(images.shape[1])
+        draws = self.draw(B, C0)
+        out = dict(batch)
+        out[KEY_IMAGES] = _intensity_launch(images, draws["params"], draws["weights"], self._seed, draws["call"])
+        return out
+
+
+def _require_intensity_input(images):
+    if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.float32 and images.dim() == 5):
+        raise RuntimeError("IntensityAugment (stroke_prediction_amd) works on (B, C, Z, Y, X) CUDA fp32 images: the transform is a set of "
+                           "HIP kernels; there is no CPU path")
+
+
+def _intensity_launch(images, params, weights, seed, call):
+    """The launches of ``IntensityAugment`` on ``images`` ((B, C0, Z, Y, X) CUDA fp32) with a host table ``params`` (B * C0, 8) and host
+    blur ``weights`` (B * C0, 2 * radius + 1) or ``None``: one pinned upload carries both, then three blur passes (only with weights),
+    the statistics and the apply launch.  Returns the new images; the input is left as it is."""
+    from stroke_prediction_amd.runtime import lib as L, ops as O
+    _require_intensity_input(images)
+    src = images.contiguous()
+    B, C0, Z, Y, X = src.shape
+    nf, per_field = B * C0, Z * Y * X
+    params = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+    if params.size != nf * 8:
+        raise ValueError("IntensityAugment: %d parameter words for %d fields of 8" % (params.size, nf))
+    host = params
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        if weights.ndim != 2 or weights.shape[0] != nf or weights.shape[1] % 2 != 1:
+            raise ValueError("IntensityAugment: blur weights are (%d, 2 * radius + 1), got %r" % (nf, weights.shape))
+        host = np.concatenate((params, weights.reshape(-1)))
+    words = torch.from_numpy(host).pin_memory().to(src.device, non_blocking=True)
+    as_i64 = lambda u: u - (1 << 64) if u >= (1 << 63) else u
+    seed, call = as_i64(int(seed) & 0xFFFFFFFFFFFFFFFF), as_i64(int(call) & 0xFFFFFFFFFFFFFFFF)
+    dst = torch.empty_like(src)
+    if weights is not None:
+        tmp = torch.empty_like(src)
+        L.call("sp_blur3d_reflect_batch", O.ptr(src), O.ptr(dst), O.ptr(tmp), O.ptr(words[nf * 8:]), nf, Z, Y, X, (weights.shape[1] - 1) // 2,
+               O.stream())
+        src = dst
+    partials = torch.empty((nf, 64, 4), dtype=torch.float32, device=src.device)
+    L.call("sp_intensity_stats_partials", O.ptr(src), O.ptr(words), O.ptr(partials), nf, per_field, seed, call, O.stream())
+    L.call("sp_intensity_apply_batch", O.ptr(src), O.ptr(dst), O.ptr(words), O.ptr(partials), nf, per_field, seed, call, O.stream())
+    return dst
 
 
 _CHAIN_ORDER = ("ResamplePlaneXY", "flip", "PadImages", "RandomPatch", "ToTensor")

@@ -97,7 +97,32 @@ _UNET = [
                                "--seed; nnU-Net uses 0.33); 0 = off")),
     ("--fgchannels", dict(type=int, nargs="+", default=None,
                           help="(MI355X build) --fgfraction: the label channels that count as foreground (default: all)")),
+    ("--intensityaugment", dict(action="store_true", default=False,
+                                help="(MI355X build) blur, noise, brightness, contrast and gamma of every training batch's images on "
+                                     "the device (data.IntensityAugment as batch_transform, seeded by --seed; the defaults are nnU-Net's); "
+                                     "works with and without --devicecache / --patchaugment / --fgfraction")),
+] + [("--ia" + name, dict(type=float, nargs=2, default=list(default), metavar=("LOW", "HIGH"),
+                          help="(MI355X build) --intensityaugment: range of the %s" % what))
+     for name, default, what in (("noisevariance", (0.0, 0.1), "noise variance (absolute: unit-scale inputs)"),
+                                 ("blursigma", (0.5, 1.0), "blur's sigma in voxels"), ("gain", (0.75, 1.25), "brightness factor"),
+                                 ("contrast", (0.75, 1.25), "contrast factor"), ("gamma", (0.7, 1.5), "gamma"))
+] + [("--iap" + name, dict(type=float, default=default, help="(MI355X build) --intensityaugment: probability per sample of %s" % what))
+     for name, default, what in (("noise", 0.1, "noise"), ("blur", 0.2, "blur"), ("blurchannel", 0.5, "blur per channel of a blurred sample"),
+                                 ("gain", 0.15, "a brightness change"), ("contrast", 0.15, "a contrast change"), ("gamma", 0.3, "gamma"),
+                                 ("gammainvert", 0.1, "the inverted gamma"))
 ]
+_IA_RANGES = ("noisevariance", "blursigma", "gain", "contrast", "gamma")
+_IA_PROBS = ("noise", "blur", "blurchannel", "gain", "contrast", "gamma", "gammainvert")
+
+
+def intensity_augment_kwargs(ns):
+    """the ``--ia*`` flags of a parsed U-Net namespace as the keyword arguments of ``data.IntensityAugment``"""
+    names = dict(noisevariance="noise_variance", blursigma="blur_sigma", blurchannel="blur_channel", gammainvert="gamma_invert")
+    kw = {names.get(n, n): tuple(getattr(ns, "ia" + n)) for n in _IA_RANGES}
+    kw.update({"p_" + names.get(n, n): getattr(ns, "iap" + n) for n in _IA_PROBS})
+    return kw
+
+
 _SDM = [
     ("unet", dict(type=str, help="Path to model of Segmentation Unet")),
     ("--channels", dict(type=int, nargs="+", default=_UNET_CHANNELS, help="Unet channels")),
@@ -139,7 +164,8 @@ class CAEParser(ExpParser):
 class UnetParser(ExpParser):
     """``--patchaugment`` samples the training patches from the device-resident case cache through a per-sample transform: it
     goes with ``--devicecache`` (the per-sample chain has no such path).  So does ``--fgfraction``: the foreground voxel is picked
-    from the cached labels."""
+    from the cached labels.  ``--intensityaugment`` is a batch transform and needs neither; its ``--ia*`` ranges and ``--iap*``
+    probabilities are checked whether or not it is given."""
     EXTRA = _UNET
 
     def parse_args(self, args=None, namespace=None):
@@ -152,6 +178,19 @@ class UnetParser(ExpParser):
         if ns.fgfraction > 0 and not ns.devicecache:
             self.error("--fgfraction needs --devicecache: the foreground voxel is picked from the labels of the device-resident case "
                        "cache (sp_patch_origins_fg); the per-sample chain has no such path")
+        for name in _IA_RANGES:
+            low, high = getattr(ns, "ia" + name)
+            if low > high:
+                self.error("--ia%s is LOW HIGH with LOW <= HIGH, got %r %r" % (name, low, high))
+            if name == "noisevariance" and low < 0:
+                self.error("--ianoisevariance is a variance: it must not be negative, got %r" % low)
+            if name != "noisevariance" and not low > 0:
+                self.error("--ia%s must be positive (%s <= 0 is no %s), got %r" % (name, name, name, low))
+        if int(4.0 * ns.iablursigma[1] + 0.5) > 64:
+            self.error("--iablursigma: a sigma of %r needs a blur radius above 64" % ns.iablursigma[1])
+        for name in _IA_PROBS:
+            if not 0 <= getattr(ns, "iap" + name) <= 1:
+                self.error("--iap%s is a probability in [0, 1], got %r" % (name, getattr(ns, "iap" + name)))
         return ns
 
 

@@ -11,28 +11,13 @@
 
 #include "sp_common.h"
 #include "sp_gauss.h"
+#include "sp_philox.h"
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
 // ------------------------------------------------------------------------------------------------ Philox4x32-10
-// Salmon et al., "Parallel random numbers: as easy as 1, 2, 3" (SC11).  Key (seed lo, seed hi); counter (e >> 2, field, call lo,
-// call hi); element e takes word e & 3 of its block: the value depends on (seed, call, field, e) alone, never on the launch.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// Philox4x32-10 (sp_philox.h).  Key (seed lo, seed hi); counter (e >> 2, field, call lo, call hi); element e takes word e & 3 of
+// its block: the value depends on (seed, call, field, e) alone, never on the launch.
 // one thread per Philox block = four consecutive elements of one field; grid (blocks per field, fields)
 __global__ __launch_bounds__(256) void rng_uniform_pm1_kernel(float* __restrict__ dst, int64_t per_field, uint32_t k0, uint32_t k1,
                                                               uint32_t call_lo, uint32_t call_hi, int vec4) {

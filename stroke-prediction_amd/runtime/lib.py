@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SP_LIB_PATH") or os.path.join(PKG_DIR, "lib", "libstr
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "stroke_amd.h")
 SOURCES = ["sp_conv.hip", "sp_conv_dma.hip", "sp_conv_par.hip", "sp_conv_zm.hip", "sp_conv_zm8.hip", "sp_wgrad.hip", "sp_wgrad_dma.hip", "sp_conv_fc.hip", "sp_wgrad_zr.hip", "sp_wgrad_pw.hip", "sp_wgrad_f8.hip", "sp_plan.hip", "sp_comm.hip", "sp_head.hip", "sp_first.hip", "sp_elem.hip", "sp_pwout.hip",
-           "sp_transform.hip", "sp_augment.hip", "sp_gather.hip", "sp_fgpatch.hip", "sp_sample.hip", "sp_ctp.hip", "sp_sdm.hip", "sp_boundary.hip", "sp_loss.hip", "sp_optim.hip"]
+           "sp_transform.hip", "sp_augment.hip", "sp_intensity.hip", "sp_gather.hip", "sp_fgpatch.hip", "sp_sample.hip", "sp_ctp.hip", "sp_sdm.hip", "sp_boundary.hip", "sp_loss.hip", "sp_optim.hip"]
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 _POINTEES = {"void", "char", "unsigned long long"}      # what the header names behind a `*` only
@@ -203,7 +203,8 @@ def build(verbose=False):
     import subprocess
     os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
     srcs = [os.path.join(CSRC_DIR, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC_DIR, "sp_common.h"), os.path.join(CSRC_DIR, "sp_edt.h"), os.path.join(CSRC_DIR, "sp_gauss.h"), HEADER]
+    hdrs = [os.path.join(CSRC_DIR, "sp_common.h"), os.path.join(CSRC_DIR, "sp_edt.h"), os.path.join(CSRC_DIR, "sp_gauss.h"),
+            os.path.join(CSRC_DIR, "sp_philox.h"), HEADER]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     jobs, links = [], []
     for variant, (fname, flags) in VARIANTS.items():

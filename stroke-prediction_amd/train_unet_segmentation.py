@@ -35,9 +35,11 @@ def build_loaders(args):
                      data.ToTensor()]
     augment = data.PatchAugment(seed=args.seed) if args.patchaugment else None
     foreground = data.ForegroundOversample(args.fgfraction, args.fgchannels, seed=args.seed) if args.fgfraction > 0 else None
+    # without --intensityaugment nothing is constructed and the factory is called exactly as before
+    extra = dict(batch_transform=data.IntensityAugment(seed=args.seed, **util.intensity_augment_kwargs(args))) if args.intensityaugment else {}
     loaders = data.get_stroke_shape_training_data(IMAGE_VOLUMES, LABEL_VOLUMES, chain(), chain(), args.fold, args.validsetsize,
                                                   seed=args.seed, batchsize=args.batchsize, device_cache=args.devicecache,
-                                                  patch_augment=augment, foreground=foreground)
+                                                  patch_augment=augment, foreground=foreground, **extra)
     print('Size training set:', len(loaders[0].sampler.indices), 'samples | Size validation set:', len(loaders[1].sampler.indices),
           'samples | Capacity batch:', args.batchsize, 'samples')
     return loaders
