@@ -42,6 +42,10 @@ __global__ __launch_bounds__(256) void conv_fc_partial_kernel(const ConvFcDev P)
   const int64_t vox = (((int64_t)b * a.Di + iz) * a.Hi + iy) * a.Wi + ix;
   const bf16_t* xp = reinterpret_cast<const bf16_t*>(a.x) + vox * (a.x_plane ? 16 : a.CPi);
   const uint4* wf = reinterpret_cast<const uint4*>(a.wfrag) + ((size_t)tap * P.spt * P.NTtot + nt0) * 64 + lane;
+  // BatchNorm groups: the scale / shift rows of this lane's sample (its group's, as conv_pw_kernel reads them)
+  const size_t cgo = a.group_batch > 0 ? (size_t)(b / a.group_batch) * a.coef_gstride : 0;
+  const float* in_sc = a.in_scale ? a.in_scale + cgo : nullptr;
+  const float* in_sh = a.in_scale ? a.in_shift + cgo : nullptr;
   f32x4 acc[FC_NTB];
 #pragma unroll
   for (int n = 0; n < FC_NTB; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -70,9 +74,9 @@ __global__ __launch_bounds__(256) void conv_fc_partial_kernel(const ConvFcDev P)
         {
           uint4 raw = bq[u];
           const int oct = s * 4 + g;
-          if (a.in_scale && inside && oct < P.octs) {
-            const float4 s0v = *reinterpret_cast<const float4*>(a.in_scale + oct * 8), s1v = *reinterpret_cast<const float4*>(a.in_scale + oct * 8 + 4);
-            const float4 h0v = *reinterpret_cast<const float4*>(a.in_shift + oct * 8), h1v = *reinterpret_cast<const float4*>(a.in_shift + oct * 8 + 4);
+          if (in_sc && inside && oct < P.octs) {
+            const float4 s0v = *reinterpret_cast<const float4*>(in_sc + oct * 8), s1v = *reinterpret_cast<const float4*>(in_sc + oct * 8 + 4);
+            const float4 h0v = *reinterpret_cast<const float4*>(in_sh + oct * 8), h1v = *reinterpret_cast<const float4*>(in_sh + oct * 8 + 4);
             const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
             const float sc[8] = {s0v.x, s0v.y, s0v.z, s0v.w, s1v.x, s1v.y, s1v.z, s1v.w};
             const float sh[8] = {h0v.x, h0v.y, h0v.z, h0v.w, h1v.x, h1v.y, h1v.z, h1v.w};
@@ -357,6 +361,7 @@ extern "C" int sp_conv_fc(const sp_conv_fc_args* a, sp_stream_t stream) {
     sp_set_error("sp_conv_fc(pointwise): no kernel for %d K steps", P.spt);
     return SP_EINVAL;
   }
+  SP_CHECK_ARG(!a->in_scale || G == 1 || a->coef_gstride % 4 == 0, "sp_conv_fc: coef_gstride %d must be a multiple of 4 floats (16-byte loads of the group rows)", a->coef_gstride);
   P.spt = ((P.octs + 3) / 4 + FC_PD - 1) / FC_PD * FC_PD;          // runtime/plan.py:fc_plan pads the same way
   P.NTtot = (a->Cout + 15) / 16;
   P.d_w = make_fastdiv(a->Wo); P.d_h = make_fastdiv(a->Ho); P.d_d = make_fastdiv(a->Do);

@@ -212,6 +212,35 @@ def test_argument_validation_refuses_before_any_gpu_work():
     assert lib.sp_allreduce_flat(None, None, 10, None) == -1 and "sp_allreduce_flat" in L.last_error()
 
 
+def test_pwout_argument_validation():
+    """sp_pwout_fwd / _bwd / _finish refuse, with a message naming the entry point, a pitch other than 16, more than 16 channels, more than
+    16 groups, coefficient rows closer than the three rows of pitch 16, and a group batch that does not divide the batch -- each with
+    every other argument valid (non-null addresses that are never dereferenced: the checks run before any GPU work)"""
+    import ctypes as C
+    lib = L.load()
+    buf = C.create_string_buffer(64)
+    p = C.addressof(buf)
+
+    def fwd(B=6, V=10, Cin=5, CP=16, coef=p, gstride=48, gb=2):
+        return lib.sp_pwout_fwd(p, B, V, Cin, CP, coef, gstride, gb, p, p, p, None), "sp_pwout_fwd"
+
+    def bwd(B=6, V=10, Cin=5, CP=16, gb=2, nrep=4):
+        return lib.sp_pwout_bwd(p, p, p, B, V, Cin, CP, p, gb, nrep, p, p, None), "sp_pwout_bwd"
+
+    def fin(nrep=4, G=3, Cin=5, coef=p, gstride=48):
+        return lib.sp_pwout_finish(p, nrep, G, Cin, p, coef, gstride, p, 4, p, p, None), "sp_pwout_finish"
+
+    SP_EINVAL = -1
+    for fn, kw in ((fwd, dict(CP=8)), (bwd, dict(CP=8)), (fwd, dict(CP=32)), (bwd, dict(CP=32)),                                  # CP != 16
+                   (fwd, dict(Cin=17)), (bwd, dict(Cin=17)), (fin, dict(Cin=17)),                                                 # Cin = 17
+                   (fin, dict(G=17)),                                                                                             # G = 17
+                   (fwd, dict(gstride=47)), (fin, dict(gstride=47)), (fwd, dict(gstride=16)), (fin, dict(gstride=0)),             # coef_gstride < 48
+                   (fwd, dict(gb=4)), (bwd, dict(gb=4)), (fwd, dict(gb=-1)), (bwd, dict(gb=-1))):                                 # group_batch does not divide B = 6
+        lib.sp_bn_stats(None, 0, 10, 8, None, None)      # (another entry point's message: the one read below is this call's own)
+        rc, name = fn(**kw)
+        assert rc == SP_EINVAL and name in L.last_error(), (name, kw, rc, L.last_error())
+
+
 def test_rccl_unique_id_through_the_c_abi():
     """sp_comm_* resolve librccl at run time; creating a unique id needs no GPU"""
     import ctypes as C

@@ -301,3 +301,30 @@ def test_parity_classes_share_one_row_tile():
                P.conv_dgrad_op(16, 24, 3, 2, 1, (28, 124, 124), 32, 16, 0)):
         assert len(op.subs) == 8
         assert len({(sb.tile["MT"], sb.tile["TD"], sb.tile["TH"]) for sb in op.subs}) == 1
+
+
+@pytest.mark.parametrize("cpi", [256, 264, 800])
+def test_split_k_plan_pads_its_k_steps_as_the_kernel_does(cpi):
+    """plan.fc_plan and sp_conv_fc (csrc/sp_conv_fc.hip) each compute the K steps per tap, padded to the kernel's prefetch depth, and
+    each says the other "pads the same way": the kernel's own expression is read from its source and evaluated beside the plan's;
+    kmap[(tap * spt + q) * 4 + g] = (src_tap << 16) | (4 q + g) for the tap's real octets, -1 in every slot past the last one"""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stroke-prediction_amd", "csrc", "sp_conv_fc.hip")).read()
+    depth = int(re.search(r"#define\s+FC_PD\s+(\d+)", src).group(1))
+    (expr,) = re.findall(r"P\.spt\s*=\s*([^;]*FC_PD[^;]*);", src)
+    assert re.fullmatch(r"[\sP.octs+\-*/()0-9FC_D]+", expr), expr
+    octs = cpi // 8
+    kernel_spt = eval(expr.replace("P.octs", str(octs)).replace("FC_PD", str(depth)).replace("/", "//"))
+    assert kernel_spt == ((octs + 3) // 4 + 3) // 4 * 4
+    op = P.convT_fwd_op(cpi, 100, 3, 1, 0, (1, 5, 6), cpi, 104, 0)
+    f = P.fc_plan(op)
+    assert f is not None and not f["pointwise"] and f["spt"] == kernel_spt and f["spt"] % depth == 0
+    taps = op.subs[0].taps
+    assert f["ntap"] == len(taps) == 27 and f["nsteps"] == 27 * f["spt"] and f["kmap"].shape == (27 * f["spt"] * 4,)
+    km = f["kmap"].reshape(27, f["spt"] * 4)
+    for ti, t in enumerate(taps):
+        np.testing.assert_array_equal(km[ti, :octs], (t[3] << 16) | np.arange(octs))
+        assert (km[ti, octs:] == -1).all() and km[ti, octs:].size == f["spt"] * 4 - octs
+        assert tuple(f["taps"][ti]) == tuple(t[:3])
+    assert sorted(t[3] for t in taps) == list(range(27))
